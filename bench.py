@@ -16,11 +16,21 @@ batches of up to `--batch-docs` documents on one engine (8 batches at N = 1).  O
 corpus: per batch, the generator seeds of its documents are set on the device, then reset +
 replay + publish, and the digests are copied out on the device.  `value` = corpus ops / step time.
 
-The default line carries that corpus too: after the config-2 leg (and its engine is freed) the
-same config-4 leg runs (`--corpus-steps` timed passes after `--corpus-warmup` untimed ones) and is
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what its headline figure needs:
+it stages the inputs, warms up, times the N steps and prints the result line (`value`,
+`ms_per_step`, the `k_replay` roofline from the events of the timed steps).  `--dump-outputs DIR`
+also writes what the last timed step computed (per-document digests, lengths and statuses, and a
+fixed seeded sample of the query batch with its answers) as DIR/<name>.npy, float64; the inputs
+are the same from run to run, so two builds can be compared array for array.
+
+`--full` adds every other leg and check to the line: the parity checks against the committed
+oracle fixtures, the CPU baselines, the text materialisation leg, the leg at BASELINE's stated
+4,096 documents, and the corpus: after the config-2 leg (and its engine is freed) the same
+config-4 leg runs (`--corpus-steps` timed passes after `--corpus-warmup` untimed ones) and is
 reported as the line's `corpus` object, with its own roofline, CPU baseline, parity and collective
-check, so `bench.py --gpus N` measures the north star's 1 M-document corpus (strong scaling over N)
-without a flag.  `--dist` initialises the RCCL process group even at world size 1.
+check, so `bench.py --full --gpus N` measures the north star's 1 M-document corpus (strong scaling
+over N) in the same run.  `--workload config4` without `--full` likewise leaves out its oracle
+sample and CPU baseline.  `--dist` initialises the RCCL process group even at world size 1.
 
 Multi-GPU: one process per GPU.  `--gpus N` with N > 1 started by hand spawns the N
 ranks through torch.distributed.run (the parent never touches a GPU); under torchrun the ranks
@@ -257,6 +267,28 @@ def golden_seq_pos(trace: str):
     n = len(b) // 5
     d = np.frombuffer(b[:4 * n], np.int32)
     return np.cumsum(d.astype(np.int64)).astype(np.uint32), np.frombuffer(b[4 * n:], np.uint8).copy()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_QUERY_SAMPLE = 1 << 19
+
+
+def u64_halves(a: np.ndarray) -> np.ndarray:
+    """u64[n] as float64[n, 2] = (high 32 bits, low 32 bits): exact, where a u64 as one float64 is not."""
+    a = np.ascontiguousarray(a, np.uint64)
+    return np.stack([a >> np.uint64(32), a & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)
+
+
+def dump_outputs(out_dir: str, arrays: dict):
+    """--dump-outputs: each array as <out_dir>/<name>.npy in float64 (every value written is an
+    integer below 2^53, so the conversion is exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, (name, total)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 TRAFFIC_WORKLOAD = {"k_replay": "automerge-paper remote, one clean launch",
@@ -556,10 +588,16 @@ def run_config4(args, world: int, rank: int, gpu: int, dist, steps: int = None, 
     ok = bool((eng.status() == 0).all()) and same and warm_ok
     # sampled documents of this rank against the oracle (global ids)
     threads, affinity, quota = cpu_share()
-    rng = np.random.default_rng(77 + rank)
-    pick = sorted(set(rng.integers(0, n, args.check_docs).tolist()) | {0, n - 1})
-    odg = oracle_digests_random(args, [lo + i for i in pick], threads)
-    ok = ok and bool(np.array_equal(dg[pick], odg))
+    pick = []
+    if args.full:
+        rng = np.random.default_rng(77 + rank)
+        pick = sorted(set(rng.integers(0, n, args.check_docs).tolist()) | {0, n - 1})
+        odg = oracle_digests_random(args, [lo + i for i in pick], threads)
+        ok = ok and bool(np.array_equal(dg[pick], odg))
+    if args.dump_outputs and rank == 0 and args.workload == "config4":
+        # the last timed pass's digests of this rank's documents (a fixed stride where they pass the limit)
+        keep = np.arange(0, n, max(1, -(-n * 24 // DUMP_MAX_BYTES)))
+        dump_outputs(args.dump_outputs, {"digests": u64_halves(dg[keep]), "digest_docs": lo + keep})
     cdev = torch.device("cpu") if args.share_gpu else dev  # (gloo rehearsal on one GPU: CPU tensors)
     t_max, per_rank, all_dg = reduce_over_ranks(elapsed, dg, dist, cdev)
     # the gather's own check: this rank's slice of the gathered digests is what it computed
@@ -585,7 +623,7 @@ def run_config4(args, world: int, rank: int, gpu: int, dist, steps: int = None, 
     line = None
     if rank == 0:
         cpu = None
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             cd, csec = cpu_baseline_random(args, threads, cpu_s)
             cpu = {"value": cd * args.gen_ops / csec, "unit": "ops/s", "cores": threads, "threads_used": threads,
                    "host_cores": os.cpu_count(), "affinity_cpus": affinity, "cgroup_cpu_quota": quota, "kind": "port",
@@ -612,9 +650,10 @@ def run_config4(args, world: int, rank: int, gpu: int, dist, steps: int = None, 
                          "alg_bytes_formula": "SURVEY 8(d): docs x (32 B x canonical spans + 24 B x ops), per batch launch",
                          "canonical_spans_per_doc": float(canon.sum()) / n},
             "cpu_baseline": cpu,
-            "parity_ok": ok,
-            "parity": f"all {D} documents' digests equal across the warm-up and timed passes; "
-                      f"{len(pick)} sampled documents per rank == the oracle's replay (global document ids)",
+            "parity_ok": ok if args.full else None,
+            "parity": (f"all {D} documents' digests equal across the warm-up and timed passes; "
+                       f"{len(pick)} sampled documents per rank == the oracle's replay (global document ids)")
+                      if args.full else "not checked (--full checks)",
             "world_size": dist.get_world_size() if dist is not None else 1,
             "collective": {"backend": dist.get_backend() if dist is not None else None,
                            "gathered_docs": int(all_dg.shape[0]), "gathered_equal_local": gathered_local},
@@ -630,6 +669,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg and check: parity against the oracle fixtures, CPU baselines, text "
+                         "materialisation, the 4,096-document leg and the 1 M-document corpus leg (default: only the "
+                         "timed steps of the headline figure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; rank 0's documents)")
     ap.add_argument("--docs", type=int, default=8192, help="documents per GPU (8 waves per SIMD)")
     ap.add_argument("--trace", default="automerge-paper")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target length of the CPU baseline sample")
@@ -659,6 +704,8 @@ def main():
                     help="rehearsal of the multi-rank path on one GPU: every rank runs its engine on cuda:0 and "
                          "the collectives go over gloo (CPU tensors); not a scaling measurement")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps only
+        args.no_cpu = args.no_text = args.no_stated_size = args.no_corpus = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -780,29 +827,42 @@ def main():
     elapsed = time.perf_counter() - t_start
     # parity: every document's state digest == the committed oracle digest, and every timed query
     # answer round-trips (loc_to_pos(pos_to_loc(p)) == p, visible, by the document's only author)
-    st = eng.status()
-    ok = bool((st == 0).all())
-    q_ok = bool(((d_p2 == d_pos) & (d_del == 0) & (d_ag == 0)).all().item()) if q else True
-    gseq = golden_pos_seq(args.trace)  # every timed pos -> loc answer against the oracle's (fixture)
-    gpos = golden_seq_pos(args.trace)  # every timed loc -> pos answer against the oracle's (fixture)
-    q_gold = q_gold_loc = None
-    if q and gseq is not None and int(lens.min()) == gseq.shape[0] == int(lens.max()):
-        g = torch.from_numpy(gseq.view(np.int32)).to(dev)
-        q_gold = bool((d_seq == g[d_pos.long()]).all().item())
-        q_ok = q_ok and q_gold
-    if q and gpos is not None:
-        gp = torch.from_numpy(gpos[0].view(np.int32)).to(dev)
-        gd = torch.from_numpy(gpos[1]).to(dev)
-        sq = d_seq.long()
-        ix = sq.clamp(0, gp.shape[0] - 1)
-        q_gold_loc = bool(((sq >= 0) & (sq < gp.shape[0])).all().item()) and \
-            bool(((d_p2 == gp[ix]) & (d_del == gd[ix])).all().item())
-        q_ok = q_ok and q_gold_loc
+    ok = q_ok = q_gold = q_gold_loc = None
+    if args.full:
+        st = eng.status()
+        ok = bool((st == 0).all())
+        q_ok = bool(((d_p2 == d_pos) & (d_del == 0) & (d_ag == 0)).all().item()) if q else True
+        gseq = golden_pos_seq(args.trace)  # every timed pos -> loc answer against the oracle's (fixture)
+        gpos = golden_seq_pos(args.trace)  # every timed loc -> pos answer against the oracle's (fixture)
+        if q and gseq is not None and int(lens.min()) == gseq.shape[0] == int(lens.max()):
+            g = torch.from_numpy(gseq.view(np.int32)).to(dev)
+            q_gold = bool((d_seq == g[d_pos.long()]).all().item())
+            q_ok = q_ok and q_gold
+        if q and gpos is not None:
+            gp = torch.from_numpy(gpos[0].view(np.int32)).to(dev)
+            gd = torch.from_numpy(gpos[1]).to(dev)
+            sq = d_seq.long()
+            ix = sq.clamp(0, gp.shape[0] - 1)
+            q_gold_loc = bool(((sq >= 0) & (sq < gp.shape[0])).all().item()) and \
+                bool(((d_p2 == gp[ix]) & (d_del == gd[ix])).all().item())
+            q_ok = q_ok and q_gold_loc
     dg = eng.digests()
     t_max, per_rank, all_dg = reduce_over_ranks(elapsed, dg, dist, torch.device("cpu") if args.share_gpu else dev)
-    gold = golden(args.trace, "remote_digest")
-    gold = int(gold, 16) if gold else None
-    ok = ok and q_ok and bool((all_dg == all_dg[0]).all()) and (gold is None or int(all_dg[0]) == gold)
+    if args.full:
+        gold = golden(args.trace, "remote_digest")
+        gold = int(gold, 16) if gold else None
+        ok = ok and q_ok and bool((all_dg == all_dg[0]).all()) and (gold is None or int(all_dg[0]) == gold)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left: every document's digest, length and status, and a fixed
+        # seeded sample of the query batch (inputs) with the answers the step wrote for it
+        arrays = {"digests": u64_halves(dg), "lens": eng.lens(), "status": eng.status()}
+        if q:
+            pick = np.unique(np.random.default_rng(2024).integers(0, n * q, min(n * q, DUMP_QUERY_SAMPLE)))
+            t_pick = torch.from_numpy(pick).to(dev)
+            for name, t in (("query_doc", d_doc), ("query_pos", d_pos), ("pos_to_loc_agent", d_ag),
+                            ("pos_to_loc_seq", d_seq), ("loc_to_pos_pos", d_p2), ("loc_to_pos_deleted", d_del)):
+                arrays[name] = t[t_pick].cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     mat = materialize_leg(eng, args.trace, n, hip, ev, s_) if not args.no_text else None
     sz = eng.export_sizes(0)
     eng.close()  # (frees the config-2 pools before the other legs allocate theirs)
@@ -856,11 +916,12 @@ def main():
                          "encoding_bytes_per_launch": enc_bytes,
                          "encoding_bytes_note": "the engine's own record stream + final raw state (not algorithmic)"},
             "cpu_baseline": cpu,
+            "full": args.full,
             "parity_ok": ok,
-            "parity": "every document's digest == committed oracle golden digest (tests/golden); every timed "
-                      "pos->loc answer == the oracle's (tests/golden/ap_remote_pos_seq.delta.gz), every timed "
-                      "loc->pos answer == the oracle's (tests/golden/ap_remote_seq_pos.delta.gz), and they "
-                      "round-trip",
+            "parity": ("every document's digest == committed oracle golden digest (tests/golden); every timed "
+                       "pos->loc answer == the oracle's (tests/golden/ap_remote_pos_seq.delta.gz), every timed "
+                       "loc->pos answer == the oracle's (tests/golden/ap_remote_seq_pos.delta.gz), and they "
+                       "round-trip") if args.full else "not checked (--full checks)",
             "queries_vs_oracle_fixture": q_gold,
             "loc_queries_vs_oracle_fixture": q_gold_loc,
             "queries_ok": q_ok,

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Convert the reference's editing traces into this repo's compact binary trace format.
 
-Test/bench input infrastructure (run once, in the build container, where /root/reference exists).
-Input : /root/reference/benchmark_data/{automerge-paper,rustcode,sveltecomponent}.json.gz
+Test/bench input infrastructure (run once).
+Input : tests/golden/benchmark_data/{automerge-paper,rustcode,sveltecomponent}.json.gz (the
+        reference's benchmark_data files, committed as fixtures)
         schema = src/testdata/src/lib.rs:10-27 ({startContent, endContent, txns:[{time, patches:[[pos, del, ins]]}]})
-Output: data/traces/<name>.trc.gz   (committed; the GPU box never sees /root/reference)
+Output: data/traces/<name>.trc.gz   (committed)
 
 Positions / lengths count Unicode scalar values, as the reference does (`chars().count()`,
 src/list/doc.rs:383). All three traces start empty.
@@ -25,7 +26,7 @@ import sys
 
 import numpy as np
 
-REF = "/root/reference/benchmark_data"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "benchmark_data")
 NAMES = ["automerge-paper", "rustcode", "sveltecomponent"]
 
 

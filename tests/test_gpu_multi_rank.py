@@ -1,5 +1,5 @@
 """The multi-rank bench path with the real engine (tests/test_multi_rank.py rehearses it on CPU
-ranks with the oracle's digests): `bench.py --gpus 2 --share-gpu` launches two ranks through
+ranks with the oracle's digests): `bench.py --full --gpus 2 --share-gpu` launches two ranks through
 torch.distributed.run exactly as `--gpus N` does, each rank replays its shard of the config-2
 corpus on its own engine (both on cuda:0 of a one-GPU box) and the digests / times meet over gloo.
 Every gathered digest must equal the committed golden digest."""
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_two_ranks_share_one_gpu():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--docs", "48",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--docs", "48",
            "--steps", "1", "--warmup", "1", "--no-cpu", "--no-text", "--queries", "256",
            "--corpus-docs", "1000", "--batch-docs", "300", "--corpus-steps", "1", "--check-docs", "4", "--gen-ops", "3000"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
@@ -37,7 +37,7 @@ def test_rccl_world_size_one():
     # launch: the corpus leg's time reduction and digest all-gather go through RCCL, and the
     # gathered digests must equal the rank's own.
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr=127.0.0.1",
-           "--master-port=29533", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist", "--workload", "config4",
+           "--master-port=29533", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--dist", "--workload", "config4",
            "--corpus-docs", "8192", "--batch-docs", "4096", "--steps", "1", "--warmup", "1", "--no-cpu",
            "--check-docs", "8", "--gen-ops", "4000"]
     env = dict(os.environ)

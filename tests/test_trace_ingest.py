@@ -6,8 +6,8 @@ pinned three ways:
     benchmark_data by tests/golden/make_traces.py with Python's json module) are re-serialised as
     JSON — ASCII-escaped (\\uXXXX, surrogate pairs) and raw UTF-8 — and must decode to the same
     counts / patches / inserted text;
-  * when /root/reference is present (the build container only), the reference's own
-    benchmark_data/*.json.gz decode to exactly the committed traces, endContent FNV included;
+  * the reference's own benchmark_data/*.json.gz (committed as fixtures under
+    tests/golden/benchmark_data/) decode to exactly the committed traces, endContent FNV included;
   * Python's json module is the checker for randomised documents and for rejection of malformed
     input.
 """
@@ -22,7 +22,7 @@ import pytest
 import crdt_amd
 from crdt_amd.traces import TRACE_NAMES, fnv1a64, ingest_json, load_trace
 
-REF_DATA = "/root/reference/benchmark_data"
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "benchmark_data")
 
 
 def _to_json_obj(t, end: str, start: str = ""):
@@ -189,7 +189,6 @@ def test_io_errors(tmp_path):
         ingest_json(str(p))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference benchmark_data only in the build container")
 @pytest.mark.parametrize("name", TRACE_NAMES)
 def test_reference_files_decode_to_committed_traces(name):
     got = ingest_json(os.path.join(REF_DATA, name + ".json.gz"))

@@ -17,6 +17,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DATA_DIR = os.path.normpath(os.path.join(_HERE, "..", "..", "data", "traces"))
+XZ_DIR = os.path.normpath(os.path.join(_HERE, "..", "..", "tests", "golden", "traces"))  # (xz-packed wire fixtures)
 TRACE_NAMES = ("automerge-paper", "rustcode", "sveltecomponent")
 
 
@@ -63,8 +64,16 @@ def load_trace(name: str, data_dir: str = DATA_DIR) -> Trace:
 
 def load_remote_wire(name: str, data_dir: str = DATA_DIR) -> bytes:
     """Remote-form (RemoteTxn wire batch) of a trace, generated offline by
-    tests/golden/make_remote.py (see include/crdt_gpu.h "Remote wire batch")."""
-    with gzip.open(os.path.join(data_dir, name + ".rtx.gz"), "rb") as f:
+    tests/golden/make_remote.py (see include/crdt_gpu.h "Remote wire batch"): <name>.rtx.gz in
+    `data_dir`, or, where the gzip form would be too large a file to commit, the fixture
+    tests/golden/traces/<name>.rtx.xz."""
+    path = os.path.join(data_dir, name + ".rtx.gz")
+    xz = os.path.join(XZ_DIR, name + ".rtx.xz")
+    if not os.path.exists(path) and os.path.exists(xz):
+        import lzma
+        with lzma.open(xz, "rb") as f:
+            return f.read()
+    with gzip.open(path, "rb") as f:
         return f.read()
 
 
