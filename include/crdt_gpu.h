@@ -133,7 +133,8 @@ int crdt_reset_async(crdt_engine* e);
 int crdt_run(crdt_engine* e, int32_t* doc_status /* n_docs, may be NULL */);
 int crdt_run_async(crdt_engine* e);   /* single launch; no growth handling */
 /* Rebuild the flat per-document index: canonical span array (stream compaction of the leaf
- * entries with YjsSpan::can_append), visible-prefix scan, order->span scatter, digests. */
+ * entries with YjsSpan::can_append), visible-prefix scan, order->span scatter.  (The digests are
+ * not part of it: crdt_digest / crdt_digest_dev_async compute them on request.) */
 int crdt_publish_async(crdt_engine* e);
 int crdt_sync(crdt_engine* e);
 
@@ -179,6 +180,40 @@ int crdt_text(crdt_engine* e, uint32_t doc, uint32_t* out, uint64_t cap, uint64_
 int crdt_text_digest(crdt_engine* e, uint64_t* per_doc /* n_docs */);
 int crdt_last_materialize_ms(crdt_engine* e, double* ms);
 
+/* ---- what a replay changed: per-document text patches between versions ---------------------
+ * No reference counterpart: with the rope's remote-delete arm todo!() (doc.rs:329-333) a caller of
+ * apply_remote_txn cannot learn what changed short of re-reading the text.
+ *
+ * A document's version is its next order (get_next_order); orders are dense and assigned in
+ * application order, so "the document at version v" is the effect of every insert item and delete
+ * op with order < v, for any 0 <= v <= version (also inside a txn).  Walk the items of the current
+ * state in document order.  An item with order x is old-visible if x < v and no delete-log entry
+ * (key, target, len) covers it with a delete order key + (x - target) < v, and new-visible if its
+ * canonical span has len > 0.  Old and new visible: closes the current patch.  Old only: adds 1 to
+ * its del_len.  New only: appended to its inserted items.  Neither: ignored.  A patch is a maximal
+ * run of old-only and new-only items; pos = new-visible items before it.  Applied front to back
+ * like crdt_local_ops, each at its pos in the text the previous ones left, the patches turn the
+ * text at version v into the current text. */
+/* next order of each listed document (get_next_order); batched form of export_sizes[10] */
+int crdt_doc_version(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* version);
+typedef struct { uint32_t pos, del_len, ins_len, ins_off; } crdt_patch;   /* ins_off: first inserted item
+                                                                             in this document's ins arrays */
+/* Compute, on the device and stream-ordered, the patches from version since[i] to now for docs[i]
+ * (publishes first if needed, like crdt_materialize_async).  docs has no duplicates.  Replaces the
+ * previous diff result.  Does not change any document.  (The call waits once inside, for the two
+ * result totals that size the result arrays.)  CRDT_E_NOMEM if an allocation fails: the engine
+ * stays usable, without a diff result. */
+int crdt_diff_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* since);
+/* Sizes of the last diff, per docs[i] of that call (syncs).  An index whose since[i] is above the
+ * document's version, or whose document is poisoned, has no result: both sizes are 0xFFFFFFFF and
+ * crdt_diff_read of it returns CRDT_E_ARG; the other indexes are not affected. */
+int crdt_diff_counts(crdt_engine* e, uint32_t* n_patches, uint32_t* n_ins);
+/* Result i of the last diff: patches[n_patches[i]], ins_order[n_ins[i]] (order of every inserted item),
+ * ins_text[n_ins[i]] (its code point through crdt_set_content, as set when the diff was computed;
+ * may be NULL; CRDT_E_ARG if asked for and the document has no content or too short a stream). */
+int crdt_diff_read(crdt_engine* e, uint64_t i, crdt_patch* patches, uint32_t* ins_order, uint32_t* ins_text);
+int crdt_last_diff_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_materialize_ms */
+
 /* ListCRDT::len (doc.rs:484-486) */
 int crdt_doc_len(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* len);
 int crdt_doc_status(crdt_engine* e, int32_t* status /* n_docs */);
@@ -213,8 +248,8 @@ int crdt_fit_note(crdt_engine* e, int apply);
 // /root/reference/src/list/doc.rs:544-569).  Device-side, async on the engine stream; the next
 // reset + crdt_run_async replays the new documents.
 int crdt_reseed_random_async(crdt_engine* e, uint64_t seed, uint64_t id_base);
-// crdt_digest into a device buffer (n_docs u64), async on the engine stream after the publish
-// that computes the digests (crdt_publish_async).
+// crdt_digest into a device buffer (n_docs u64), async on the engine stream: publishes first if
+// needed, then computes the digests of the published state (on request, as crdt_digest does).
 int crdt_digest_dev_async(crdt_engine* e, uint64_t* dev_out);
 // on != 0: documents staged in one call from the same host stream (crdt_stage_local_shared,
 // crdt_stage_remote_replicated) read one device copy of it instead of a copy each (records

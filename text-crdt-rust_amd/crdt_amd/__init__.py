@@ -279,6 +279,11 @@ def lib():
     L.crdt_text.argtypes = [vp, u32, P(u32), u64, P(u64)]
     L.crdt_text_digest.argtypes = [vp, P(u64)]
     L.crdt_last_materialize_ms.argtypes = [vp, P(C.c_double)]
+    L.crdt_doc_version.argtypes = [vp, u64, P(u32), P(u32)]
+    L.crdt_diff_async.argtypes = [vp, u64, P(u32), P(u32)]
+    L.crdt_diff_counts.argtypes = [vp, P(u32), P(u32)]
+    L.crdt_diff_read.argtypes = [vp, u64, vp, P(u32), P(u32)]
+    L.crdt_last_diff_ms.argtypes = [vp, P(C.c_double)]
     L.crdt_last_error.restype = C.c_char_p
     L.crdt_trace_load.argtypes = [C.c_char_p, P(vp)]
     L.crdt_trace_parse.argtypes = [C.c_char_p, u64, P(vp)]
@@ -300,6 +305,7 @@ EXPORTED_SYMBOLS = [
     "crdt_stage_local_shared", "crdt_set_content", "crdt_materialize_async", "crdt_text", "crdt_text_digest",
     "crdt_last_materialize_ms", "crdt_set_content_copies", "crdt_canon_counts", "crdt_fit", "crdt_mem_bytes", "crdt_apply_local_probed", "crdt_set_share_streams", "crdt_set_device_intern", "crdt_set_query_kernel", "crdt_device_bytes",
     "crdt_fit_note", "crdt_reseed_random_async", "crdt_digest_dev_async", "crdt_test_fail_alloc_after",
+    "crdt_doc_version", "crdt_diff_async", "crdt_diff_counts", "crdt_diff_read", "crdt_last_diff_ms",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -634,6 +640,64 @@ class Engine:
         self.L.crdt_last_materialize_ms(self.h, C.byref(x))
         return x.value
 
+    # --- what a replay changed: text patches from a past version to now (crdt_gpu.h "what a replay changed")
+    def versions(self, docs=None) -> np.ndarray:
+        """next order of every listed document (get_next_order): the version diff() counts from"""
+        d = np.arange(self.n_docs, dtype=np.uint32) if docs is None else np.ascontiguousarray(docs, dtype=np.uint32)
+        out = np.zeros(d.shape[0], np.uint32)
+        _check(self.L.crdt_doc_version(self.h, d.shape[0], _p(d), _p(out)), "doc_version")
+        return out
+
+    def diff_async(self, docs, since):
+        """compute the patches from version since[i] to now for docs[i] (no duplicates) on the device"""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        s = np.ascontiguousarray(since, dtype=np.uint32)
+        if d.shape != s.shape or d.ndim != 1:
+            raise ValueError("diff: docs and since are 1-d and of equal length")
+        _check(self.L.crdt_diff_async(self.h, d.shape[0], _p(d), _p(s)), "diff_async")
+        self._diff_n = d.shape[0]
+
+    def diff_counts(self):
+        """(n_patches, n_ins) per index of the last diff_async; 0xFFFFFFFF marks an index without a
+        result (since above the document's version, or a poisoned document)"""
+        n = getattr(self, "_diff_n", 0)
+        npat, nins = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        _check(self.L.crdt_diff_counts(self.h, _p(npat), _p(nins)), "diff_counts")
+        return npat, nins
+
+    def diff_read(self, i: int, counts=None, text: bool = True):
+        """result i of the last diff_async: (patches [n, 4] u32 = (pos, del_len, ins_len, ins_off),
+        ins_order, ins_text or None); raises CrdtError (rc=-100) for an index without a result"""
+        npat, nins = counts if counts is not None else self.diff_counts()
+        bad = not 0 <= i < len(npat) or int(npat[i]) == 0xFFFFFFFF  # (the library answers CRDT_E_ARG)
+        pat = np.zeros((0 if bad else int(npat[i]), 4), np.uint32)
+        io = np.zeros(0 if bad else int(nins[i]), np.uint32)
+        _check(self.L.crdt_diff_read(self.h, i, pat.ctypes.data, _p(io), None), "diff_read")
+        it = None
+        if text:
+            it = np.zeros_like(io)
+            if self.L.crdt_diff_read(self.h, i, None, None, _p(it)) != 0:
+                it = None  # (no content, or too short a stream, for this document)
+        return pat, io, it
+
+    def diff(self, docs, since, strict: bool = True):
+        """[(patches (n, 4) u32, ins_order, ins_text or None)] per docs[i]: the patches that turn the
+        text of docs[i] at version since[i] into its current text.  An index without a result
+        (since above the version, a poisoned document) raises CrdtError, or is None with
+        strict=False; the other indexes are not affected."""
+        self.diff_async(docs, since)
+        counts = self.diff_counts()
+        bad = np.flatnonzero(counts[0] == 0xFFFFFFFF)
+        if strict and bad.size:
+            raise CrdtError(f"diff failed rc=-100 for indexes {bad.tolist()}: since above the version, or a poisoned document")
+        return [None if int(counts[0][i]) == 0xFFFFFFFF else self.diff_read(i, counts) for i in range(len(counts[0]))]
+
+    def diff_ms(self) -> float:
+        """device time of the last diff (HIP events)"""
+        x = C.c_double()
+        _check(self.L.crdt_last_diff_ms(self.h, C.byref(x)), "last_diff_ms")
+        return x.value
+
     def timings(self):
         a, b = C.c_double(), C.c_double()
         self.L.crdt_last_timings(self.h, C.byref(a), C.byref(b))
@@ -673,6 +737,14 @@ class ListCRDT:
 
     def __len__(self) -> int:                                   # doc.rs:484
         return int(self.e.lens([0])[0])
+
+    def version(self) -> int:                                   # get_next_order
+        return int(self.e.versions([0])[0])
+
+    def diff_since(self, v: int):
+        """(patches [n, 4] u32 = (pos, del_len, ins_len, ins_off), ins_order, ins_text or None): what
+        turns the text at version `v` (an earlier version()) into the current text"""
+        return self.e.diff([0], [v])[0]
 
     def status(self) -> int:
         return int(self.e.status()[0])

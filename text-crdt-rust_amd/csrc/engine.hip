@@ -38,16 +38,18 @@ std::mutex g_mem_mu;
 std::unordered_map<void*, u64> g_mem_size;
 u64 g_mem_cur = 0, g_mem_peak = 0;
 long long g_fail_alloc_after = -1;  // crdt_test_fail_alloc_after: the allocations left before one fails
+thread_local bool g_alloc_oom = false;  // a dalloc of this thread ran out of memory since the flag was cleared
 template <class T>
 hipError_t dalloc(T*& p, u64 n) {
   p = nullptr;
   if (n == 0) n = 1;
   {
     std::lock_guard<std::mutex> g(g_mem_mu);
-    if (g_fail_alloc_after == 0) return hipErrorOutOfMemory;
+    if (g_fail_alloc_after == 0) { g_alloc_oom = true; return hipErrorOutOfMemory; }
     if (g_fail_alloc_after > 0) g_fail_alloc_after--;
   }
   hipError_t e = hipMalloc((void**)&p, sizeof(T) * n);
+  if (e == hipErrorOutOfMemory) g_alloc_oom = true;
   if (e == hipSuccess) {
     std::lock_guard<std::mutex> g(g_mem_mu);
     g_mem_size[(void*)p] = sizeof(T) * n;
@@ -258,6 +260,28 @@ struct crdt_engine {
   // query scratch
   void* qbuf = nullptr;
   u64 qbuf_bytes = 0;
+  // diff (crdt_diff_async): the listed documents, their versions to diff from and bitmap bases
+  // (host copies live until the next call: they are the source of asynchronous uploads), the
+  // "deleted before since" bitmaps, the per-index results and the result arrays; all kept and
+  // grown from call to call
+  hipEvent_t ev_diff[2] = {nullptr, nullptr};
+  std::vector<u32> diff_docs_h, diff_since_h;
+  std::vector<u64> diff_bm_h;
+  std::vector<DiffRes> diff_res_h;
+  u32* diff_docs = nullptr;
+  u32* diff_since = nullptr;
+  u64* diff_bm_base = nullptr;
+  DiffRes* diff_res = nullptr;
+  u64* diff_tot = nullptr;
+  u32* diff_bm = nullptr;
+  Patch* diff_pat = nullptr;
+  u32* diff_io = nullptr;
+  u32* diff_it = nullptr;
+  u64 diff_n_cap = 0, diff_bm_cap = 0, diff_pat_cap = 0, diff_ins_cap = 0;
+  u64 diff_n = 0;
+  bool diff_valid = false;   // a diff result exists (crdt_diff_async succeeded since the last crdt_docs_alloc)
+  bool diff_pulled = false;  // ... and diff_res_h / last_diff_ms hold it
+  double last_diff_ms = 0;
 
   Pools pools_view(const PoolSet& ps) const {
     Pools p{};
@@ -321,6 +345,11 @@ struct crdt_engine {
     if (qbuf) (void)hipFree(qbuf);
     qbuf = nullptr;
     qbuf_bytes = 0;
+    dfree(diff_docs); dfree(diff_since); dfree(diff_bm_base); dfree(diff_res); dfree(diff_tot); dfree(diff_bm);
+    dfree(diff_pat); dfree(diff_io); dfree(diff_it);
+    diff_n_cap = diff_bm_cap = diff_pat_cap = diff_ins_cap = 0;
+    diff_n = 0;
+    diff_valid = diff_pulled = false;
   }
 
   int set_device() {
@@ -1232,7 +1261,125 @@ struct crdt_engine {
     qbuf_bytes = bytes;
     return 0;
   }
+
+  DiffIO diff_view() const {
+    DiffIO io{};
+    io.docs = diff_docs;
+    io.since = diff_since;
+    io.bm_base = diff_bm_base;
+    io.bm = diff_bm;
+    io.res = diff_res;
+    io.patches = diff_pat;
+    io.ins_order = diff_io;
+    io.ins_text = diff_it;
+    io.content = content;
+    io.cbase = cbase;
+    io.clen = clen;
+    return io;
+  }
+  // A diff buffer for `need` entries (contents not kept).  The stream is drained before the old
+  // one goes: the previous diff's kernels may still use it.
+  template <class T>
+  int diff_grow(T*& p, u64& cap, u64 need) {
+    if (p && need <= cap) return 0;
+    HIPCHK(hipStreamSynchronize(stream));
+    dfree(p);
+    cap = 0;
+    HIPCHK(dalloc(p, need));
+    cap = std::max<u64>(need, 1);
+    return 0;
+  }
+  // crdt_diff_async: mark the deletes below each version, count every document's patches and
+  // inserted items, scan the counts into offsets on the device, size the result arrays from the
+  // two totals (the one host read between the passes: 16 bytes), write the results.
+  int diff(u64 n, const uint32_t* dl, const uint32_t* since) {
+    int r = set_device();
+    if (r) return r;
+    diff_valid = diff_pulled = false;
+    if (!published) {
+      r = publish();
+      if (r) return r;
+    }
+    diff_n = n;
+    if (!n) {
+      diff_valid = true;
+      return 0;
+    }
+    diff_docs_h.assign(dl, dl + n);
+    diff_since_h.assign(since, since + n);
+    diff_bm_h.resize(n);
+    u64 words = 0;
+    u32 xw = 0;           // the largest listed bitmap that k_diff_mark builds in LDS
+    bool all_lds = true;  // ... and every listed one is (no bitmap word needs zeroing)
+    for (u64 i = 0; i < n; i++) {
+      diff_bm_h[i] = words;
+      u32 nw = pub_words(seg_h[dl[i]].ord_cap);
+      words += nw;
+      if (nw <= DIFF_MARK_WORDS) xw = std::max(xw, nw);
+      else all_lds = false;
+    }
+    if (n > diff_n_cap) {
+      HIPCHK(hipStreamSynchronize(stream));
+      dfree(diff_docs); dfree(diff_since); dfree(diff_bm_base); dfree(diff_res);
+      diff_n_cap = 0;
+      HIPCHK(dalloc(diff_docs, n));
+      HIPCHK(dalloc(diff_since, n));
+      HIPCHK(dalloc(diff_bm_base, n));
+      HIPCHK(dalloc(diff_res, n));
+      diff_n_cap = n;
+    }
+    if (!diff_tot) HIPCHK(dalloc(diff_tot, 2));
+    r = diff_grow(diff_bm, diff_bm_cap, words);
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(diff_docs, diff_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(diff_since, diff_since_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(diff_bm_base, diff_bm_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(ev_diff[0], stream));
+    if (!all_lds) HIPCHK(hipMemsetAsync(diff_bm, 0, words * 4, stream));
+    Pools pv = pools_view(pools);
+    PubOut ov = pub_view();
+    hipLaunchKernelGGL(k_diff_mark, dim3((u32)n), dim3(DIFF_T), (size_t)xw * 4, stream, pv, diff_view(), (u32)n, xw);
+    hipLaunchKernelGGL(k_diff<false>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, diff_view(), (u32)n);
+    hipLaunchKernelGGL(k_diff_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, diff_res, (u32)n, diff_tot);
+    HIPCHK(hipGetLastError());
+    u64 tot[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(tot, diff_tot, 16, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    r = diff_grow(diff_pat, diff_pat_cap, tot[0]);
+    if (r) return r;
+    if (!diff_io || !diff_it || tot[1] > diff_ins_cap) {
+      dfree(diff_io); dfree(diff_it);
+      diff_ins_cap = 0;
+      HIPCHK(dalloc(diff_io, tot[1]));
+      HIPCHK(dalloc(diff_it, tot[1]));
+      diff_ins_cap = std::max<u64>(tot[1], 1);
+    }
+    hipLaunchKernelGGL(k_diff<true>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, diff_view(), (u32)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev_diff[1], stream));
+    diff_valid = true;
+    return 0;
+  }
+  // the per-index results and the device time of the last diff, on the host (waits for it)
+  int diff_finish() {
+    if (!diff_valid) return CRDT_E_ARG;
+    if (diff_pulled) return 0;
+    int r = set_device();
+    if (r) return r;
+    diff_res_h.resize(diff_n);
+    last_diff_ms = 0;
+    if (diff_n) {
+      HIPCHK(hipMemcpyAsync(diff_res_h.data(), diff_res, diff_n * sizeof(DiffRes), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, ev_diff[0], ev_diff[1]);
+      last_diff_ms = ms;
+    }
+    diff_pulled = true;
+    return 0;
+  }
 };
+static_assert(sizeof(Patch) == sizeof(crdt_patch) && sizeof(crdt_patch) == 16, "crdt_patch is the kernels' Patch");
 
 static bool valid(const crdt_engine* e) { return e && e->n_docs > 0; }
 static bool poisoned(const crdt_engine* e) {
@@ -1283,7 +1430,10 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
   (void)hipFuncSetAttribute((const void*)k_loc_to_pos_blk<4>, hipFuncAttributeMaxDynamicSharedMemorySize, QBLK_W * 8u);
   (void)hipFuncSetAttribute((const void*)k_pub_index, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)pubx_lds_bytes(PUBX_MAX_WORDS));
+  (void)hipFuncSetAttribute((const void*)k_diff_mark, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIFF_MARK_WORDS * 4u));
   for (auto& x : e->ev)
+    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
+  for (auto& x : e->ev_diff)
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   *out = e.release();
   return 0;
@@ -1295,6 +1445,8 @@ void crdt_engine_destroy(crdt_engine* e) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   e->release();
   for (auto& x : e->ev)
+    if (x) (void)hipEventDestroy(x);
+  for (auto& x : e->ev_diff)
     if (x) (void)hipEventDestroy(x);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -2015,7 +2167,8 @@ int crdt_device_bytes(uint64_t* current, uint64_t* peak, int reset_peak) {
 uint64_t crdt_mem_bytes(const crdt_engine* e) {
   if (!e) return 0;
   return e->pools.bytes + e->rec_cap * sizeof(Rec) + e->content_cap * 4 + e->text_cap * 4 + e->canon_alloc * 28 +
-         e->pub_alloc * 4 + e->probe_cap * 16 +
+         e->pub_alloc * 4 + e->probe_cap * 16 + e->diff_bm_cap * 4 + e->diff_pat_cap * sizeof(Patch) + e->diff_ins_cap * 8 +
+         e->diff_n_cap * (4 + 4 + 8 + sizeof(DiffRes)) +
          e->n_docs * (sizeof(DocState) + sizeof(DocSeg) + 4 + 4 + 8);
 }
 
@@ -2076,6 +2229,73 @@ int crdt_text_digest(crdt_engine* e, uint64_t* per_doc) {
 int crdt_last_materialize_ms(crdt_engine* e, double* ms) {
   if (!e || !ms) return CRDT_E_ARG;
   *ms = e->last_materialize_ms;
+  return 0;
+}
+
+int crdt_doc_version(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* version) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n && (!doc || !version))) return CRDT_E_ARG;
+  int r = e->pull_states();
+  if (r) return r;
+  for (uint64_t i = 0; i < n; i++) {
+    if (doc[i] >= e->n_docs) return CRDT_E_ARG;
+    version[i] = e->st_h[doc[i]].next_order;
+  }
+  return 0;
+}
+
+int crdt_diff_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* since) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n_docs && (!docs || !since)) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
+  g_alloc_oom = false;
+  int r = e->diff(n_docs, docs, since);
+  // (no relayout is involved: an allocation that fails leaves the engine as it was, without a diff result)
+  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
+  return r;
+}
+
+int crdt_diff_counts(crdt_engine* e, uint32_t* n_patches, uint32_t* n_ins) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->diff_finish();
+  if (r) return r;
+  for (u64 i = 0; i < e->diff_n; i++) {
+    const DiffRes& x = e->diff_res_h[i];
+    bool bad = (x.flags & DIFF_BAD) != 0;
+    if (n_patches) n_patches[i] = bad ? INVALID : x.n_pat;
+    if (n_ins) n_ins[i] = bad ? INVALID : x.n_ins;
+  }
+  return 0;
+}
+
+int crdt_diff_read(crdt_engine* e, uint64_t i, crdt_patch* patches, uint32_t* ins_order, uint32_t* ins_text) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->diff_finish();
+  if (r) return r;
+  if (i >= e->diff_n) return CRDT_E_ARG;
+  const DiffRes& x = e->diff_res_h[i];
+  if (x.flags & DIFF_BAD) {
+    g_last_error = "diff: since above the document's version, or a poisoned document";
+    return CRDT_E_ARG;
+  }
+  if (ins_text && !(x.flags & DIFF_TEXT)) {
+    g_last_error = "diff: the document has no content (or too short a stream) for ins_text";
+    return CRDT_E_ARG;
+  }
+  if (patches && x.n_pat) HIPCHK(hipMemcpy(patches, e->diff_pat + x.poff, (u64)x.n_pat * sizeof(Patch), hipMemcpyDeviceToHost));
+  if (ins_order && x.n_ins) HIPCHK(hipMemcpy(ins_order, e->diff_io + x.ioff, (u64)x.n_ins * 4, hipMemcpyDeviceToHost));
+  if (ins_text && x.n_ins) HIPCHK(hipMemcpy(ins_text, e->diff_it + x.ioff, (u64)x.n_ins * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int crdt_last_diff_ms(crdt_engine* e, double* ms) {
+  if (!e || !ms) return CRDT_E_ARG;
+  if (e->diff_valid && !e->diff_pulled) {
+    int r = e->diff_finish();
+    if (r) return r;
+  }
+  *ms = e->last_diff_ms;
   return 0;
 }
 

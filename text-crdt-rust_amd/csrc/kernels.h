@@ -7,6 +7,8 @@
 //   k_pub_index the order->span index of k_publish's documents, built in LDS (block per document)
 //   k_pos_to_loc / k_loc_to_pos   batched lookups on the published index (thread per query)
 //   k_materialize  document text from the published index + content streams (block per document)
+//   k_diff_mark / k_diff / k_diff_scan  per-document text patches from a past version to now, from
+//               the published index + the delete log (block per listed document)
 #pragma once
 #include "replay_core.h"
 #include "wave_gpu.h"
@@ -934,6 +936,295 @@ __global__ __launch_bounds__(64 * MAT_WAVES) void k_materialize(Pools P, PubOut 
     u32 len = O.len[d];
     T.tlen[d] = len;
     T.tdigest[d] = mix64(hs ^ ((u64)len << 32 | 0x54ull));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Per-document diff (crdt_diff_async): the patches that turn a document's text at version `since`
+// (every insert item and delete op with order < since applied) into its current text, from the
+// published index and the delete log.  No reference counterpart: the reference's rope arm for
+// remote deletes is todo!() (doc.rs:329-333), so a caller of apply_remote_txn cannot learn what
+// changed.  Walk the items in document order; an item with order x is
+//   old-visible: x < since and no delete-log run covers it with a delete order < since;
+//   new-visible: its canonical span has len > 0.
+// K (both) closes the current patch, D (old only) adds to its del_len, I (new only) appends to
+// its inserted items, N (neither) is ignored.  A patch is a maximal run of D and I items; its pos
+// is the number of new-visible items before it.
+//
+// Per canonical span this is closed form.  A visible span is never in the delete log, so it is
+// K^k I^i with k = its orders below `since`; a deleted span is D^d with d = its orders below
+// `since` whose bit in the "deleted before since" bitmap (k_diff_mark) is clear, the rest N.
+// A patch starts at a span with d + i > 0 that has k > 0 or whose last predecessor with any K, D
+// or I item ended on a K; patch p's del_len / ins_len are the D / I items between its start and
+// the next patch's start.
+// ---------------------------------------------------------------------------------------------
+struct Patch { u32 pos, del_len, ins_len, ins_off; };  // crdt_patch (include/crdt_gpu.h)
+constexpr u32 DIFF_BAD = 1u;    // since > version, or a poisoned document: no result for this index
+constexpr u32 DIFF_TEXT = 2u;   // ins_text was written (the document has content for all its orders)
+struct DiffRes {
+  u32 n_pat, n_ins, flags, version;
+  u64 poff, ioff;  // first patch / first inserted item of this index in the result arrays (k_diff_scan)
+};
+struct DiffIO {
+  const u32* docs;     // [i] the listed documents
+  const u32* since;    // [i]
+  const u64* bm_base;  // [i] first word of the index's bitmap in bm
+  u32* bm;             // bit (x & 31) of word x >> 5: a delete op with order < since covers item x
+                       // (pub_words(ord_cap) words per index, zeroed per call)
+  DiffRes* res;        // [i]
+  Patch* patches;      // [res[i].poff + p]
+  u32* ins_order;      // [res[i].ioff + j]
+  u32* ins_text;       // [res[i].ioff + j]
+  const u32* content;  // TextIO's content streams
+  const u64* cbase;
+  const u64* clen;
+};
+#define DIFF_T 256u       // threads per document: k_diff walks DIFF_T canonical spans per loop pass
+#define DIFF_WAVES 4u
+#define DIFF_LONG 256u    // deleted spans with more orders below `since` are counted by the whole wave
+
+// bits [a, b) that fall into word w (a < b; the range's words are a >> 5 .. (b - 1) >> 5)
+__device__ __forceinline__ u32 range_mask(u32 w, u32 a, u32 b) {
+  u32 lo = w == (a >> 5) ? (a & 31u) : 0u;
+  u32 hi = w == ((b - 1u) >> 5) ? ((b - 1u) & 31u) : 31u;
+  return (0xFFFFFFFFu << lo) & (0xFFFFFFFFu >> (31u - hi));
+}
+
+// The delete log's runs with key < since, clipped at since (a run that straddles it counts with
+// its part below), scattered into the index's order-indexed bitmap: lanes take runs, one atomic
+// OR of the combined mask per word.  A bitmap of at most xw words (the launch's dynamic LDS; the
+// host passes the largest listed bitmap up to DIFF_MARK_WORDS) is built in LDS and stored whole;
+// a larger one takes the atomics in HBM, on words the host zeroed.  (8,192 AP documents, half
+// the log: 7.5 ms with every atomic in HBM.)
+#define DIFF_MARK_WORDS 16384u  // 64 KiB of LDS: bitmaps up to 524,256 orders
+__global__ __launch_bounds__(DIFF_T) void k_diff_mark(Pools P, DiffIO D, u32 n, u32 xw) {
+  u32 i = blockIdx.x;
+  if (i >= n) return;
+  u32 d = D.docs[i];
+  i32 stt = P.st[d].status;
+  u32 no = P.st[d].next_order, v = D.since[i];
+  if ((stt != ST_OK && stt != ST_NEED_CAPACITY) || v > no) return;
+  const DocSeg& sg = P.seg[d];
+  u32 ord_cap = sg.ord_cap;  // > every order: word (ord_cap - 1) >> 5 is inside the bitmap
+  u32 nw = pub_words(ord_cap);
+  const DelRun* dels = P.dels + sg.del_base;
+  u32* bm = D.bm + D.bm_base[i];
+  // the runs with key < since: the log is in key order
+  u32 lo = 0, hi = min(P.st[d].n_del, sg.del_cap);
+  while (lo < hi) {
+    u32 mid = (lo + hi) >> 1;
+    if (dels[mid].key < v) lo = mid + 1u;
+    else hi = mid;
+  }
+  u32 nd = lo;
+  bool in_lds = nw <= xw;
+  if (in_lds) {
+    for (u32 w = threadIdx.x; w < nw; w += DIFF_T) s_dyn[w] = 0u;
+    __syncthreads();
+  }
+  for (u32 r = threadIdx.x; r < nd; r += DIFF_T) {
+    DelRun q = dels[r];
+    if (q.key >= v || q.order >= ord_cap) continue;
+    u32 m = min(q.len, v - q.key);
+    u32 a = q.order, b = (u32)min((u64)q.order + m, (u64)ord_cap);
+    if (a >= b) continue;
+    if (in_lds) {
+      for (u32 w = a >> 5; w <= ((b - 1u) >> 5); w++) atomicOr(&s_dyn[w], range_mask(w, a, b));
+    } else {
+      for (u32 w = a >> 5; w <= ((b - 1u) >> 5); w++) atomicOr(&bm[w], range_mask(w, a, b));
+    }
+  }
+  if (in_lds) {
+    __syncthreads();
+    for (u32 w = threadIdx.x; w < nw; w += DIFF_T) bm[w] = s_dyn[w];
+  }
+}
+
+// Exclusive scan of the indexes' patch and inserted-item counts into their result offsets (one
+// block; thread t takes a contiguous slice of the indexes); totals[0 / 1] = patches / items.
+#define DIFF_SCAN_T 1024u
+__global__ __launch_bounds__(DIFF_SCAN_T) void k_diff_scan(DiffRes* res, u32 n, u64* totals) {
+  __shared__ u64 s_p[DIFF_SCAN_T], s_i[DIFF_SCAN_T];
+  u32 t = threadIdx.x;
+  u32 per = (n + DIFF_SCAN_T - 1u) / DIFF_SCAN_T;
+  u64 lo = min((u64)t * per, (u64)n), hi = min(lo + per, (u64)n);
+  u64 ap = 0, ai = 0;
+  for (u64 k = lo; k < hi; k++) { ap += res[k].n_pat; ai += res[k].n_ins; }
+  s_p[t] = ap;
+  s_i[t] = ai;
+  __syncthreads();
+  if (t == 0) {
+    ap = ai = 0;
+    for (u32 x = 0; x < DIFF_SCAN_T; x++) {
+      u64 p = s_p[x], q = s_i[x];
+      s_p[x] = ap; s_i[x] = ai;
+      ap += p; ai += q;
+    }
+    totals[0] = ap;
+    totals[1] = ai;
+  }
+  __syncthreads();
+  ap = s_p[t];
+  ai = s_i[t];
+  for (u64 k = lo; k < hi; k++) {
+    u32 p = res[k].n_pat, q = res[k].n_ins;
+    res[k].poff = ap; res[k].ioff = ai;
+    ap += p; ai += q;
+  }
+}
+
+// One block per listed document, DIFF_T canonical spans per loop pass, in document order.
+// WRITE = false counts the document's patches and inserted items (res[i]); WRITE = true, after
+// k_diff_scan, writes them.  Within a pass each thread classifies its span (k, d, i above), wave
+// scans give the D / I items and patch starts before it, and the waves' totals meet in LDS; the
+// "is a patch open" state, the patch count and the D / I counts carry from pass to pass in
+// registers (every thread folds the same LDS totals).  The start span of patch p writes its pos,
+// its ins_off and, for now, the D items before it into ins_len; a last sweep over the document's
+// patches turns neighbouring starts into del_len and ins_len.
+template <bool WRITE>
+__global__ __launch_bounds__(DIFF_T) void k_diff(Pools P, PubOut O, DiffIO D, u32 n) {
+  u32 i = blockIdx.x;
+  if (i >= n) return;
+  u32 d = D.docs[i];
+  u32 tid = threadIdx.x, l = lane_id(), wv = uni(tid >> 6);
+  i32 stt = P.st[d].status;
+  u32 no = P.st[d].next_order, v = D.since[i];
+  u64 cb = D.cbase[d], cl = D.clen[d];
+  bool text = cb != NO_CONTENT && cl >= (u64)no;
+  if ((stt != ST_OK && stt != ST_NEED_CAPACITY) || v > no) {
+    if (!WRITE && tid == 0) D.res[i] = DiffRes{0u, 0u, DIFF_BAD, no, 0ull, 0ull};
+    return;
+  }
+  const DocSeg& sg = P.seg[d];
+  u64 cbase = sg.canon_base;
+  const Span* cn = O.canon + cbase;
+  const u32* vp = O.vpos + cbase;
+  u32 ns = min(O.canon_n[d], sg.canon_cap);
+  const u32* bm = D.bm + D.bm_base[i];
+  u32 my_pat = 0, my_ins = 0;  // (WRITE) this index's counts from the first pass: every store stays below them
+  Patch* pat = nullptr;
+  u32* io = nullptr;
+  u32* it = nullptr;
+  if (WRITE) {
+    DiffRes rs = D.res[i];
+    my_pat = rs.n_pat; my_ins = rs.n_ins;
+    pat = D.patches + rs.poff;
+    io = D.ins_order + rs.ioff;
+    it = D.ins_text + rs.ioff;
+  }
+  const u32* src = D.content + (text ? cb : 0ull);
+  __shared__ u32 s_op[DIFF_WAVES], s_d[DIFF_WAVES], s_i[DIFF_WAVES], s_st[DIFF_WAVES];
+  u32 c_open = 0, c_pat = 0, c_del = 0, c_ins = 0;  // carried: a patch is open; patches, D and I items so far
+  for (u32 k0 = 0; k0 < ns; k0 += DIFF_T) {
+    u32 k = k0 + tid;
+    Span sp = k < ns ? cn[k] : Span{0, 0, 0, 0};
+    u32 ln = slen(sp);
+    u32 below = sp.order < v ? min(ln, v - sp.order) : 0u;  // the span's orders below `since`
+    u32 kk = 0, dd = 0, ii = 0;
+    if (sp.len > 0) { kk = below; ii = ln - below; }
+    // deleted span: its orders [a, b) below `since` that no earlier delete covers are D items
+    u32 a = sp.order, b = sp.order + (sp.len < 0 ? below : 0u);
+    u32 cnt = b - a;
+    if (cnt != 0u && cnt <= DIFF_LONG) {
+      u32 set = 0;
+      for (u32 w = a >> 5; w <= ((b - 1u) >> 5); w++) set += (u32)__popc(bm[w] & range_mask(w, a, b));
+      dd = cnt - set;
+    }
+    u64 big = ballot(cnt > DIFF_LONG);
+    while (big) {  // long ones: the wave's lanes take words
+      u32 s = (u32)__builtin_ctzll(big);
+      big &= big - 1ull;
+      u32 ua = rdlane(a, s), ub = rdlane(b, s);
+      u32 set = 0;
+      for (u32 w = (ua >> 5) + l; w <= ((ub - 1u) >> 5); w += 64u) set += (u32)__popc(bm[w] & range_mask(w, ua, ub));
+      set = wave_sum(set);
+      if (l == s) dd = (ub - ua) - set;
+    }
+    bool c = (dd + ii) != 0u, bk = kk != 0u;
+    // patch state after each span: content opens (or keeps open) a patch, a K-only span closes it
+    u64 mO = ballot(c), mC = ballot(bk && !c);
+    u32 Di = wave_incl_scan(dd), Ii = wave_incl_scan(ii);
+    if (l == 63u) {
+      s_d[wv] = Di;
+      s_i[wv] = Ii;
+      s_op[wv] = (mO | mC) ? (mO > mC ? 1u : 2u) : 0u;  // (the higher lane decides) 0: no K, D or I item in this wave
+    }
+    __syncthreads();
+    u32 open_in = c_open, d_in = c_del, i_in = c_ins;
+    for (u32 w = 0; w < wv; w++) {
+      u32 op = s_op[w];
+      if (op) open_in = op == 1u;
+      d_in += s_d[w];
+      i_in += s_i[w];
+    }
+    u64 lower = (1ull << l) - 1ull;
+    u64 lo = mO & lower, lc = mC & lower;
+    bool open_before = (lo | lc) ? lo > lc : open_in != 0u;
+    bool start = c && (bk || !open_before);
+    u64 mS = ballot(start);
+    if (l == 0u) s_st[wv] = (u32)__popcll(mS);
+    __syncthreads();
+    if (WRITE) {
+      u32 p = c_pat + (u32)__popcll(mS & lower);
+      for (u32 w = 0; w < wv; w++) p += s_st[w];
+      u32 Dex = d_in + Di - dd, Iex = i_in + Ii - ii;  // D / I items before this span
+      if (start && p < my_pat) pat[p] = Patch{vp[k] + kk, 0u, Dex, Iex};
+      // the wave's inserted items: lane l takes item t + l of the wave's Tn, so stores are
+      // contiguous; its span is the first lane whose inclusive count passes it (a 6-step search
+      // over the scan through ds_bpermute; lanes without inserted items repeat their
+      // predecessor's count and are never found)
+      u32 fo = sp.order + kk;  // the span's first inserted order
+      u32 st = Ii - ii;        // its first item within the wave
+      u32 Tn = rdlane(Ii, 63);
+      u32 wbase = Iex - st;    // I items before this wave (the same in every lane)
+      for (u32 t = 0; t < Tn; t += 64u) {
+        u32 j = t + l;
+        u32 s = 0;
+#pragma unroll
+        for (u32 step = 32u; step >= 1u; step >>= 1) s += shfl(Ii, s + step - 1u) <= j ? step : 0u;
+        u32 sfo = shfl(fo, s), sst = shfl(st, s);
+        u32 x = wbase + j, o = sfo + (j - sst);
+        if (j < Tn && x < my_ins) {
+          io[x] = o;
+          if (text) it[x] = src[o];
+        }
+      }
+    }
+    for (u32 w = 0; w < DIFF_WAVES; w++) {
+      u32 op = s_op[w];
+      if (op) c_open = op == 1u;
+      c_del += s_d[w];
+      c_ins += s_i[w];
+      c_pat += s_st[w];
+    }
+    __syncthreads();  // (the next pass rewrites the LDS totals)
+  }
+  if (!WRITE) {
+    if (tid == 0) D.res[i] = DiffRes{c_pat, c_ins, text ? DIFF_TEXT : 0u, no, 0ull, 0ull};
+    return;
+  }
+  // del_len / ins_len of patch p: the D / I items from its start to the next patch's start (the
+  // document's totals after the last one).  Each sweep reads its patches and their successors,
+  // then writes; the next sweep's patches are untouched until then.
+  u32 np = min(c_pat, my_pat);
+  __syncthreads();
+  for (u32 p0 = 0; p0 < np; p0 += DIFF_T) {
+    u32 p = p0 + tid;
+    u32 d0 = 0, d1 = 0, i0 = 0, i1 = 0;
+    if (p < np) {
+      Patch x = pat[p];
+      d0 = x.ins_len; i0 = x.ins_off;
+      d1 = c_del; i1 = c_ins;
+      if (p + 1u < np) {
+        Patch y = pat[p + 1u];
+        d1 = y.ins_len; i1 = y.ins_off;
+      }
+    }
+    __syncthreads();
+    if (p < np) {
+      pat[p].del_len = d1 - d0;
+      pat[p].ins_len = i1 - i0;
+    }
   }
 }
 
