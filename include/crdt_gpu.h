@@ -214,6 +214,49 @@ int crdt_diff_counts(crdt_engine* e, uint32_t* n_patches, uint32_t* n_ins);
 int crdt_diff_read(crdt_engine* e, uint64_t i, crdt_patch* patches, uint32_t* ins_order, uint32_t* ins_text);
 int crdt_last_diff_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_materialize_ms */
 
+/* ---- documents at a past version: text and position queries --------------------------------
+ * No reference counterpart (the reference keeps no history of its rope).  "The document at version
+ * v" is the sequence of old-visible items of the definition above, in document order, for any
+ * 0 <= v <= version (also inside a txn); its text is their code points, its length their count,
+ * its position p the p-th of them.  An item with order >= v does not exist at v.  For the same
+ * application order this is the state of a replay that stopped at v.
+ *
+ * Build the views of docs[i] at version[i] on the device, stream-ordered (publishes first if
+ * needed).  docs has no duplicates.  Replaces the previous checkout; changes no document and not
+ * the diff result.  (The call waits once inside, for the total that sizes the result arrays.)
+ * CRDT_E_NOMEM if an allocation fails: the engine stays usable, without a checkout. */
+int crdt_checkout_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* version);
+/* Length of every index of the last checkout (syncs).  An index whose version[i] is above the
+ * document's version, or whose document is poisoned, has no result: its length is 0xFFFFFFFF, and
+ * crdt_checkout_read of it and a host-form query that names it return CRDT_E_ARG; the other
+ * indexes are not affected. */
+int crdt_checkout_lens(crdt_engine* e, uint32_t* len);
+/* View i: order[len[i]] (the order of every item, in document order) and text[len[i]] (its code
+ * point through crdt_set_content, as set when the checkout was computed; may be NULL; CRDT_E_ARG
+ * if asked for and the document has no content or too short a stream).  The arrays are copies:
+ * they stay readable until the next checkout or crdt_docs_alloc, whatever happens to the documents. */
+int crdt_checkout_read(crdt_engine* e, uint64_t i, uint32_t* order, uint32_t* text);
+/* Text digest of every index (the function of crdt_text_digest; 0 without content or result). */
+int crdt_checkout_digest(crdt_engine* e, uint64_t* per_index);
+/* The README's two mappings on the views: idx[q] names an index of the last checkout; answers as
+ * crdt_pos_to_loc / crdt_loc_to_pos (invalid position: agent 0xFFFF, seq 0xFFFFFFFF; deleted 0/1,
+ * 2 = unknown id, which an id whose order is >= v is).  An idx out of range, or one without a
+ * result, gives CRDT_E_ARG for the whole call and writes nothing.  The queries also read the
+ * published index: CRDT_E_ARG once any document was replayed, staged and run, reset or published
+ * again since the checkout. */
+int crdt_pos_to_loc_at(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, uint16_t* agent,
+                       uint32_t* seq);
+int crdt_loc_to_pos_at(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint16_t* agent, const uint32_t* seq,
+                       uint32_t* pos, uint8_t* deleted);
+/* Device-pointer forms (inputs/outputs already in HBM; async on the engine stream).  idx cannot be
+ * checked on the host: a query whose idx is out of range or has no result is answered as an
+ * invalid position / an unknown id. */
+int crdt_pos_to_loc_at_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos,
+                                 uint16_t* agent, uint32_t* seq);
+int crdt_loc_to_pos_at_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint16_t* agent,
+                                 const uint32_t* seq, uint32_t* pos, uint8_t* deleted);
+int crdt_last_checkout_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
+
 /* ListCRDT::len (doc.rs:484-486) */
 int crdt_doc_len(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* len);
 int crdt_doc_status(crdt_engine* e, int32_t* status /* n_docs */);

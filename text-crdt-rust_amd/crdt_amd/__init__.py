@@ -284,6 +284,15 @@ def lib():
     L.crdt_diff_counts.argtypes = [vp, P(u32), P(u32)]
     L.crdt_diff_read.argtypes = [vp, u64, vp, P(u32), P(u32)]
     L.crdt_last_diff_ms.argtypes = [vp, P(C.c_double)]
+    L.crdt_checkout_async.argtypes = [vp, u64, P(u32), P(u32)]
+    L.crdt_checkout_lens.argtypes = [vp, P(u32)]
+    L.crdt_checkout_read.argtypes = [vp, u64, P(u32), P(u32)]
+    L.crdt_checkout_digest.argtypes = [vp, P(u64)]
+    L.crdt_pos_to_loc_at.argtypes = [vp, u64, P(u32), P(u32), P(C.c_uint16), P(u32)]
+    L.crdt_loc_to_pos_at.argtypes = [vp, u64, P(u32), P(C.c_uint16), P(u32), P(u32), P(C.c_uint8)]
+    L.crdt_pos_to_loc_at_dev_async.argtypes = [vp, u64, vp, vp, vp, vp]
+    L.crdt_loc_to_pos_at_dev_async.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+    L.crdt_last_checkout_ms.argtypes = [vp, P(C.c_double)]
     L.crdt_last_error.restype = C.c_char_p
     L.crdt_trace_load.argtypes = [C.c_char_p, P(vp)]
     L.crdt_trace_parse.argtypes = [C.c_char_p, u64, P(vp)]
@@ -306,6 +315,8 @@ EXPORTED_SYMBOLS = [
     "crdt_last_materialize_ms", "crdt_set_content_copies", "crdt_canon_counts", "crdt_fit", "crdt_mem_bytes", "crdt_apply_local_probed", "crdt_set_share_streams", "crdt_set_device_intern", "crdt_set_query_kernel", "crdt_device_bytes",
     "crdt_fit_note", "crdt_reseed_random_async", "crdt_digest_dev_async", "crdt_test_fail_alloc_after",
     "crdt_doc_version", "crdt_diff_async", "crdt_diff_counts", "crdt_diff_read", "crdt_last_diff_ms",
+    "crdt_checkout_async", "crdt_checkout_lens", "crdt_checkout_read", "crdt_checkout_digest", "crdt_pos_to_loc_at",
+    "crdt_loc_to_pos_at", "crdt_pos_to_loc_at_dev_async", "crdt_loc_to_pos_at_dev_async", "crdt_last_checkout_ms",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -698,6 +709,79 @@ class Engine:
         _check(self.L.crdt_last_diff_ms(self.h, C.byref(x)), "last_diff_ms")
         return x.value
 
+    # --- documents at a past version (crdt_gpu.h "documents at a past version")
+    def checkout_async(self, docs, versions):
+        """build the views of docs[i] (no duplicates) at versions[i] on the device; replaces the last checkout"""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        v = np.ascontiguousarray(versions, dtype=np.uint32)
+        if d.shape != v.shape or d.ndim != 1:
+            raise ValueError("checkout: docs and versions are 1-d and of equal length")
+        _check(self.L.crdt_checkout_async(self.h, d.shape[0], _p(d), _p(v)), "checkout_async")
+        self._co_n = d.shape[0]
+
+    def checkout_lens(self) -> np.ndarray:
+        """length of every index of the last checkout_async; 0xFFFFFFFF marks an index without a result
+        (version above the document's version, or a poisoned document)"""
+        out = np.zeros(getattr(self, "_co_n", 0), np.uint32)
+        _check(self.L.crdt_checkout_lens(self.h, _p(out)), "checkout_lens")
+        return out
+
+    def checkout_read(self, i: int, lens=None, text: bool = True):
+        """view i of the last checkout_async: (order of every item in document order, their code points
+        or None); raises CrdtError (rc=-100) for an index without a result"""
+        lens = lens if lens is not None else self.checkout_lens()
+        bad = not 0 <= i < len(lens) or int(lens[i]) == 0xFFFFFFFF  # (the library answers CRDT_E_ARG)
+        order = np.zeros(0 if bad else int(lens[i]), np.uint32)
+        _check(self.L.crdt_checkout_read(self.h, i, _p(order), None), "checkout_read")
+        tx = None
+        if text:
+            tx = np.zeros_like(order)
+            if self.L.crdt_checkout_read(self.h, i, None, _p(tx)) != 0:
+                tx = None  # (no content, or too short a stream, for this document)
+        return order, tx
+
+    def checkout(self, docs, versions, strict: bool = True):
+        """[(order, text or None)] per docs[i]: the document at version versions[i].  An index without
+        a result raises CrdtError, or is None with strict=False; the other indexes are not affected."""
+        self.checkout_async(docs, versions)
+        lens = self.checkout_lens()
+        bad = np.flatnonzero(lens == 0xFFFFFFFF)
+        if strict and bad.size:
+            raise CrdtError(f"checkout failed rc=-100 for indexes {bad.tolist()}: version above the document's, or a poisoned document")
+        return [None if int(lens[i]) == 0xFFFFFFFF else self.checkout_read(i, lens) for i in range(len(lens))]
+
+    def checkout_digests(self) -> np.ndarray:
+        """text digest of every index of the last checkout (0: no content, or no result)"""
+        out = np.zeros(getattr(self, "_co_n", 0), np.uint64)
+        _check(self.L.crdt_checkout_digest(self.h, _p(out, C.c_uint64)), "checkout_digest")
+        return out
+
+    def pos_to_loc_at(self, idx, pos):
+        """pos_to_loc on the views of the last checkout: idx[q] names an index of it"""
+        i = np.ascontiguousarray(idx, dtype=np.uint32)
+        p = np.ascontiguousarray(pos, dtype=np.uint32)
+        a = np.zeros(p.shape[0], np.uint16)
+        s = np.zeros(p.shape[0], np.uint32)
+        _check(self.L.crdt_pos_to_loc_at(self.h, p.shape[0], _p(i), _p(p), _p(a, C.c_uint16), _p(s)), "pos_to_loc_at")
+        return a, s
+
+    def loc_to_pos_at(self, idx, agent, seq):
+        """loc_to_pos on the views of the last checkout (deleted: 0/1, 2 = not known at that version)"""
+        i = np.ascontiguousarray(idx, dtype=np.uint32)
+        a = np.ascontiguousarray(agent, dtype=np.uint16)
+        s = np.ascontiguousarray(seq, dtype=np.uint32)
+        p = np.zeros(s.shape[0], np.uint32)
+        dl = np.zeros(s.shape[0], np.uint8)
+        _check(self.L.crdt_loc_to_pos_at(self.h, s.shape[0], _p(i), _p(a, C.c_uint16), _p(s), _p(p), _p(dl, C.c_uint8)),
+               "loc_to_pos_at")
+        return p, dl
+
+    def checkout_ms(self) -> float:
+        """device time of the last checkout (HIP events)"""
+        x = C.c_double()
+        _check(self.L.crdt_last_checkout_ms(self.h, C.byref(x)), "last_checkout_ms")
+        return x.value
+
     def timings(self):
         a, b = C.c_double(), C.c_double()
         self.L.crdt_last_timings(self.h, C.byref(a), C.byref(b))
@@ -745,6 +829,17 @@ class ListCRDT:
         """(patches [n, 4] u32 = (pos, del_len, ins_len, ins_off), ins_order, ins_text or None): what
         turns the text at version `v` (an earlier version()) into the current text"""
         return self.e.diff([0], [v])[0]
+
+    def text_at(self, v: int) -> np.ndarray:
+        """the text (UTF-32 code points) at version `v` (an earlier version(); needs set_content)"""
+        tx = self.e.checkout([0], [v])[0][1]
+        if tx is None:
+            raise CrdtError("text_at failed rc=-100: the document has no content (or too short a stream)")
+        return tx
+
+    def to_string_at(self, v: int) -> str:
+        from .traces import utf32_to_str
+        return utf32_to_str(self.text_at(v))
 
     def status(self) -> int:
         return int(self.e.status()[0])

@@ -282,6 +282,30 @@ struct crdt_engine {
   bool diff_valid = false;   // a diff result exists (crdt_diff_async succeeded since the last crdt_docs_alloc)
   bool diff_pulled = false;  // ... and diff_res_h / last_diff_ms hold it
   double last_diff_ms = 0;
+  // checkout (crdt_checkout_async): buffers of its own, kept and grown from call to call like the
+  // diff's.  The arrays are copies and stay readable; the _at queries also read the published
+  // index, so they need pub_epoch (counts publishes) unchanged and the index still current.
+  hipEvent_t ev_co[2] = {nullptr, nullptr};
+  std::vector<u32> co_docs_h, co_ver_h;
+  std::vector<u64> co_bm_h, co_sp_h;
+  std::vector<CoRes> co_res_h;
+  u32* co_docs = nullptr;
+  u32* co_ver = nullptr;
+  u64* co_bm_base = nullptr;
+  u64* co_sp_base = nullptr;
+  CoRes* co_res = nullptr;
+  u64* co_tot = nullptr;
+  u32* co_bm = nullptr;
+  u32* co_rk = nullptr;
+  u32* co_opos = nullptr;
+  u32* co_ord = nullptr;
+  u32* co_text = nullptr;
+  u64 co_n_cap = 0, co_bm_cap = 0, co_rk_cap = 0, co_opos_cap = 0, co_out_cap = 0;
+  u64 co_n = 0;
+  bool co_valid = false;   // a checkout exists (crdt_checkout_async succeeded since the last crdt_docs_alloc)
+  bool co_pulled = false;  // ... and co_res_h / last_co_ms hold it
+  double last_co_ms = 0;
+  u64 pub_epoch = 0, co_epoch = 0;
 
   Pools pools_view(const PoolSet& ps) const {
     Pools p{};
@@ -350,6 +374,11 @@ struct crdt_engine {
     diff_n_cap = diff_bm_cap = diff_pat_cap = diff_ins_cap = 0;
     diff_n = 0;
     diff_valid = diff_pulled = false;
+    dfree(co_docs); dfree(co_ver); dfree(co_bm_base); dfree(co_sp_base); dfree(co_res); dfree(co_tot);
+    dfree(co_bm); dfree(co_rk); dfree(co_opos); dfree(co_ord); dfree(co_text);
+    co_n_cap = co_bm_cap = co_rk_cap = co_opos_cap = co_out_cap = 0;
+    co_n = 0;
+    co_valid = co_pulled = false;
   }
 
   int set_device() {
@@ -1112,6 +1141,7 @@ struct crdt_engine {
     }
     HIPCHK(hipEventRecord(ev[3], stream));
     published = true;
+    pub_epoch++;  // (a checkout's _at queries read this index: they hold for one publish)
     digested = false;
     materialized = false;
     return 0;
@@ -1378,6 +1408,130 @@ struct crdt_engine {
     diff_pulled = true;
     return 0;
   }
+
+  CoIO co_view() const {
+    CoIO io{};
+    io.docs = co_docs;
+    io.version = co_ver;
+    io.bm_base = co_bm_base;
+    io.bm = co_bm;
+    io.rk = co_rk;
+    io.sp_base = co_sp_base;
+    io.opos = co_opos;
+    io.res = co_res;
+    io.ord = co_ord;
+    io.text = co_text;
+    io.content = content;
+    io.cbase = cbase;
+    io.clen = clen;
+    return io;
+  }
+  // crdt_checkout_async: mark the deletes below each version (k_diff_mark on the checkout's own
+  // buffers), rank the bitmaps, count every view's items per span (opos) and in all, scan the
+  // lengths into offsets on the device, size the two item arrays from the total (the one host read:
+  // 8 bytes), write the items.
+  int checkout(u64 n, const uint32_t* dl, const uint32_t* ver) {
+    int r = set_device();
+    if (r) return r;
+    co_valid = co_pulled = false;
+    if (!published) {
+      r = publish();
+      if (r) return r;
+    }
+    co_n = n;
+    co_epoch = pub_epoch;
+    if (!n) {
+      co_valid = true;
+      return 0;
+    }
+    co_docs_h.assign(dl, dl + n);
+    co_ver_h.assign(ver, ver + n);
+    co_bm_h.resize(n);
+    co_sp_h.resize(n);
+    u64 words = 0, spans = 0;
+    u32 xw = 0;           // the largest listed bitmap that k_diff_mark builds in LDS
+    bool all_lds = true;  // ... and every listed one is (no bitmap word needs zeroing)
+    for (u64 i = 0; i < n; i++) {
+      co_bm_h[i] = words;
+      co_sp_h[i] = spans;
+      u32 nw = pub_words(seg_h[dl[i]].ord_cap);
+      words += nw;
+      spans += seg_h[dl[i]].canon_cap;
+      if (nw <= DIFF_MARK_WORDS) xw = std::max(xw, nw);
+      else all_lds = false;
+    }
+    if (n > co_n_cap) {
+      HIPCHK(hipStreamSynchronize(stream));
+      dfree(co_docs); dfree(co_ver); dfree(co_bm_base); dfree(co_sp_base); dfree(co_res);
+      co_n_cap = 0;
+      HIPCHK(dalloc(co_docs, n));
+      HIPCHK(dalloc(co_ver, n));
+      HIPCHK(dalloc(co_bm_base, n));
+      HIPCHK(dalloc(co_sp_base, n));
+      HIPCHK(dalloc(co_res, n));
+      co_n_cap = n;
+    }
+    if (!co_tot) HIPCHK(dalloc(co_tot, 1));
+    r = diff_grow(co_bm, co_bm_cap, words);
+    if (r) return r;
+    r = diff_grow(co_rk, co_rk_cap, words);
+    if (r) return r;
+    r = diff_grow(co_opos, co_opos_cap, spans);
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(co_docs, co_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(co_ver, co_ver_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(co_bm_base, co_bm_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(co_sp_base, co_sp_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(ev_co[0], stream));
+    if (!all_lds) HIPCHK(hipMemsetAsync(co_bm, 0, words * 4, stream));
+    Pools pv = pools_view(pools);
+    PubOut ov = pub_view();
+    DiffIO mark{};  // k_diff_mark reads these four only
+    mark.docs = co_docs;
+    mark.since = co_ver;
+    mark.bm_base = co_bm_base;
+    mark.bm = co_bm;
+    hipLaunchKernelGGL(k_diff_mark, dim3((u32)n), dim3(DIFF_T), (size_t)xw * 4, stream, pv, mark, (u32)n, xw);
+    hipLaunchKernelGGL(k_co_rank, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, co_view(), (u32)n);
+    hipLaunchKernelGGL(k_co_count, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, co_view(), (u32)n);
+    hipLaunchKernelGGL(k_co_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, co_res, (u32)n, co_tot);
+    HIPCHK(hipGetLastError());
+    u64 tot = 0;
+    HIPCHK(hipMemcpyAsync(&tot, co_tot, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (!co_ord || !co_text || tot > co_out_cap) {
+      dfree(co_ord); dfree(co_text);
+      co_out_cap = 0;
+      HIPCHK(dalloc(co_ord, tot));
+      HIPCHK(dalloc(co_text, tot));
+      co_out_cap = std::max<u64>(tot, 1);
+    }
+    hipLaunchKernelGGL(k_co_write, dim3((u32)n), dim3(64 * CO_WAVES), 0, stream, pv, ov, co_view(), (u32)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev_co[1], stream));
+    co_valid = true;
+    return 0;
+  }
+  // the per-index results and the device time of the last checkout, on the host (waits for it)
+  int co_finish() {
+    if (!co_valid) return CRDT_E_ARG;
+    if (co_pulled) return 0;
+    int r = set_device();
+    if (r) return r;
+    co_res_h.resize(co_n);
+    last_co_ms = 0;
+    if (co_n) {
+      HIPCHK(hipMemcpyAsync(co_res_h.data(), co_res, co_n * sizeof(CoRes), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, ev_co[0], ev_co[1]);
+      last_co_ms = ms;
+    }
+    co_pulled = true;
+    return 0;
+  }
+  // the _at queries' precondition: a checkout whose published index is still the current one
+  bool co_fresh() const { return co_valid && published && co_epoch == pub_epoch; }
 };
 static_assert(sizeof(Patch) == sizeof(crdt_patch) && sizeof(crdt_patch) == 16, "crdt_patch is the kernels' Patch");
 
@@ -1435,6 +1589,8 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   for (auto& x : e->ev_diff)
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
+  for (auto& x : e->ev_co)
+    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   *out = e.release();
   return 0;
 }
@@ -1447,6 +1603,8 @@ void crdt_engine_destroy(crdt_engine* e) {
   for (auto& x : e->ev)
     if (x) (void)hipEventDestroy(x);
   for (auto& x : e->ev_diff)
+    if (x) (void)hipEventDestroy(x);
+  for (auto& x : e->ev_co)
     if (x) (void)hipEventDestroy(x);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -2169,6 +2327,8 @@ uint64_t crdt_mem_bytes(const crdt_engine* e) {
   return e->pools.bytes + e->rec_cap * sizeof(Rec) + e->content_cap * 4 + e->text_cap * 4 + e->canon_alloc * 28 +
          e->pub_alloc * 4 + e->probe_cap * 16 + e->diff_bm_cap * 4 + e->diff_pat_cap * sizeof(Patch) + e->diff_ins_cap * 8 +
          e->diff_n_cap * (4 + 4 + 8 + sizeof(DiffRes)) +
+         (e->co_bm_cap + e->co_rk_cap + e->co_opos_cap + 2 * e->co_out_cap) * 4 +
+         e->co_n_cap * (4 + 4 + 8 + 8 + sizeof(CoRes)) +
          e->n_docs * (sizeof(DocState) + sizeof(DocSeg) + 4 + 4 + 8);
 }
 
@@ -2296,6 +2456,163 @@ int crdt_last_diff_ms(crdt_engine* e, double* ms) {
     if (r) return r;
   }
   *ms = e->last_diff_ms;
+  return 0;
+}
+
+int crdt_checkout_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* version) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n_docs && (!docs || !version)) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
+  g_alloc_oom = false;
+  int r = e->checkout(n_docs, docs, version);
+  // (no relayout is involved: an allocation that fails leaves the engine as it was, without a checkout)
+  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
+  return r;
+}
+
+int crdt_checkout_lens(crdt_engine* e, uint32_t* len) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->co_finish();
+  if (r) return r;
+  for (u64 i = 0; len && i < e->co_n; i++) len[i] = (e->co_res_h[i].flags & CO_BAD) ? INVALID : e->co_res_h[i].len;
+  return 0;
+}
+
+// result i of the last checkout, or nullptr (with the error text set) when the index has none
+static const CoRes* co_result(crdt_engine* e, uint64_t i) {
+  if (i >= e->co_n) return nullptr;
+  const CoRes& x = e->co_res_h[i];
+  if (x.flags & CO_BAD) {
+    g_last_error = "checkout: version above the document's version, or a poisoned document";
+    return nullptr;
+  }
+  return &x;
+}
+
+int crdt_checkout_read(crdt_engine* e, uint64_t i, uint32_t* order, uint32_t* text) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->co_finish();
+  if (r) return r;
+  const CoRes* x = co_result(e, i);
+  if (!x) return CRDT_E_ARG;
+  if (text && !(x->flags & CO_TEXT)) {
+    g_last_error = "checkout: the document has no content (or too short a stream) for text";
+    return CRDT_E_ARG;
+  }
+  if (order && x->len) HIPCHK(hipMemcpy(order, e->co_ord + x->off, (u64)x->len * 4, hipMemcpyDeviceToHost));
+  if (text && x->len) HIPCHK(hipMemcpy(text, e->co_text + x->off, (u64)x->len * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int crdt_checkout_digest(crdt_engine* e, uint64_t* per_index) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->co_finish();
+  if (r) return r;
+  for (u64 i = 0; per_index && i < e->co_n; i++) per_index[i] = (e->co_res_h[i].flags & CO_BAD) ? 0ull : e->co_res_h[i].digest;
+  return 0;
+}
+
+int crdt_last_checkout_ms(crdt_engine* e, double* ms) {
+  if (!e || !ms) return CRDT_E_ARG;
+  if (e->co_valid && !e->co_pulled) {
+    int r = e->co_finish();
+    if (r) return r;
+  }
+  *ms = e->last_co_ms;
+  return 0;
+}
+
+static int co_query_ok(crdt_engine* e) {
+  if (!e->co_fresh()) {
+    g_last_error = "checkout: no checkout, or a document changed (or was re-published) since it";
+    return CRDT_E_ARG;
+  }
+  return 0;
+}
+
+int crdt_pos_to_loc_at_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, uint16_t* agent,
+                                 uint32_t* seq) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = co_query_ok(e);
+  if (r) return r;
+  if (!n) return 0;
+  u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_pos_to_loc_at, dim3(blocks), dim3(256), 0, e->stream, e->pools_view(e->pools), e->co_view(), (u32)e->co_n, n,
+                     idx, pos, agent, seq);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int crdt_loc_to_pos_at_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint16_t* agent, const uint32_t* seq,
+                                 uint32_t* pos, uint8_t* deleted) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = co_query_ok(e);
+  if (r) return r;
+  if (!n) return 0;
+  u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_loc_to_pos_at, dim3(blocks), dim3(256), 0, e->stream, e->pools_view(e->pools), e->pub_view(), e->co_view(),
+                     (u32)e->co_n, n, idx, agent, seq, pos, deleted);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the host forms name only indexes that have a result (checked before anything is written)
+static int co_idx_ok(crdt_engine* e, uint64_t n, const uint32_t* idx) {
+  int r = co_query_ok(e);
+  if (r) return r;
+  r = e->co_finish();
+  if (r) return r;
+  for (uint64_t q = 0; q < n; q++)
+    if (!co_result(e, idx[q])) return CRDT_E_ARG;
+  return 0;
+}
+
+int crdt_pos_to_loc_at(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, uint16_t* agent, uint32_t* seq) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n && (!idx || !pos || !agent || !seq))) return CRDT_E_ARG;
+  int r = co_idx_ok(e, n, idx);
+  if (r || !n) return r;
+  r = e->scratch(n * (4 + 4 + 2 + 4) + 64);
+  if (r) return r;
+  u32* d_idx = (u32*)e->qbuf;
+  u32* d_pos = d_idx + n;
+  u32* d_seq = d_pos + n;
+  u16* d_ag = (u16*)(d_seq + n);
+  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_pos, pos, n * 4, hipMemcpyHostToDevice, e->stream));
+  r = crdt_pos_to_loc_at_dev_async(e, n, d_idx, d_pos, d_ag, d_seq);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(agent, d_ag, n * 2, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(seq, d_seq, n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int crdt_loc_to_pos_at(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint16_t* agent, const uint32_t* seq, uint32_t* pos,
+                       uint8_t* deleted) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n && (!idx || !agent || !seq || !pos || !deleted))) return CRDT_E_ARG;
+  int r = co_idx_ok(e, n, idx);
+  if (r || !n) return r;
+  r = e->scratch(n * (4 + 4 + 4 + 2 + 1) + 64);
+  if (r) return r;
+  u32* d_idx = (u32*)e->qbuf;
+  u32* d_seq = d_idx + n;
+  u32* d_pos = d_seq + n;
+  u16* d_ag = (u16*)(d_pos + n);
+  u8* d_del = (u8*)(d_ag + n);
+  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_seq, seq, n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_ag, agent, n * 2, hipMemcpyHostToDevice, e->stream));
+  r = crdt_loc_to_pos_at_dev_async(e, n, d_idx, d_ag, d_seq, d_pos, d_del);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(pos, d_pos, n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(deleted, d_del, n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 }
 

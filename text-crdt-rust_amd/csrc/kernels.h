@@ -9,6 +9,9 @@
 //   k_materialize  document text from the published index + content streams (block per document)
 //   k_diff_mark / k_diff / k_diff_scan  per-document text patches from a past version to now, from
 //               the published index + the delete log (block per listed document)
+//   k_co_rank / k_co_count / k_co_scan / k_co_write  the document at a past version (checkout): its
+//               items' orders and text, from the same inputs (block per listed document)
+//   k_pos_to_loc_at / k_loc_to_pos_at   the two lookups on a checked-out view (thread per query)
 #pragma once
 #include "replay_core.h"
 #include "wave_gpu.h"
@@ -1549,6 +1552,311 @@ __global__ void k_loc_to_pos(Pools P, PubOut O, u32 n_docs, u64 nq, const u32* d
             Span sp = O.canon[seg.canon_base + k];
             ps = O.vpos[seg.canon_base + k] + (sp.len > 0 ? order - sp.order : 0u);
             dl = sp.len < 0 ? 1 : 0;
+          }
+        }
+      }
+    }
+    pos[q] = ps;
+    deleted[q] = dl;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Checkout (crdt_checkout_async): the document at a past version v -- the old-visible items of
+// the diff's definition above, in document order -- as arrays (order and code point of every
+// item) plus a per-span prefix `opos` that answers the two README mappings on that view.  From
+// the published index and the delete log only; no reference counterpart (the reference keeps no
+// history of its rope).
+//
+// k_diff_mark (as it is, on the checkout's own buffers) gives the "deleted before v" bitmap;
+// k_co_rank adds a rank directory, rk[w] = set bits in words [0, w), so the set bits of any
+// order range below v are two lookups.  The old-visible items of canonical span [a, a + n) are
+// then its orders below v minus the set bits among them: closed form for a visible span (never
+// in the delete log: no bit set) and for a deleted span of any length alike.
+// ---------------------------------------------------------------------------------------------
+constexpr u32 CO_BAD = 1u;    // version > the document's version, or a poisoned document: no result
+constexpr u32 CO_TEXT = 2u;   // text and digest were written (the document has content for all its orders)
+struct CoRes {
+  u32 len, flags, version, at;  // old-visible items; CO_*; the document's version; v
+  u64 off;                      // first item of this index in ord / text (k_co_scan)
+  u64 digest;                   // text digest (text_hash per item, as k_materialize; 0 without content)
+};
+struct CoIO {
+  const u32* docs;     // [i] the listed documents
+  const u32* version;  // [i] v
+  const u64* bm_base;  // [i] first word of the index's bitmap in bm / rk
+  const u32* bm;       // k_diff_mark's bitmap: bit x set = a delete op with order < v covers item x
+  u32* rk;             // [bm_base[i] + w] set bits in words [0, w) of the index's bitmap, w <= v >> 5
+  const u64* sp_base;  // [i] first entry of the index in opos (canon_cap entries each)
+  u32* opos;           // [sp_base[i] + k] old-visible items before canonical span k (vpos of the view)
+  CoRes* res;          // [i]
+  u32* ord;            // [res[i].off + p] order of item p of the view
+  u32* text;           // [res[i].off + p] its code point
+  const u32* content;  // TextIO's content streams
+  const u64* cbase;
+  const u64* clen;
+};
+#define CO_WAVES 4u
+
+// set bits below order x (x <= v: word x >> 5 has a directory entry)
+__device__ __forceinline__ u32 co_set_below(const u32* bm, const u32* rk, u32 x) {
+  u32 w = x >> 5;
+  return rk[w] + (u32)__popc(bm[w] & ((1u << (x & 31u)) - 1u));
+}
+// old-visible items of a canonical span at version v
+__device__ __forceinline__ u32 co_span_count(const Span& sp, u32 v, const u32* bm, const u32* rk) {
+  u32 below = sp.order < v ? min(slen(sp), v - sp.order) : 0u;
+  if (sp.len > 0 || below == 0u) return below;
+  return below - (co_set_below(bm, rk, sp.order + below) - co_set_below(bm, rk, sp.order));
+}
+// index of the n-th (from 0) set bit of m; m has more than n set bits
+__device__ __forceinline__ u32 select32(u32 m, u32 n) {
+  u32 pos = 0;
+#pragma unroll
+  for (u32 s = 16u; s >= 1u; s >>= 1) {
+    u32 c = (u32)__popc((m >> pos) & ((1u << s) - 1u));
+    if (n >= c) { n -= c; pos += s; }
+  }
+  return pos;
+}
+// the listed document has a view at v: it is alive, v is no later than its version, and its
+// orders fit the published bitmap (publish sizes ord_cap above next_order)
+__device__ __forceinline__ bool co_ok(const Pools& P, u32 d, u32 v, u32& no) {
+  i32 stt = P.st[d].status;
+  no = P.st[d].next_order;
+  return (stt == ST_OK || stt == ST_NEED_CAPACITY) && v <= no && no < P.seg[d].ord_cap;
+}
+
+// The rank directory of words [0, v >> 5] of every listed bitmap, one block per index: a
+// streaming block scan, 8 consecutive words per thread and pass (the waves' totals meet in LDS,
+// the carry stays in registers).  The bitmap is read once, straight after k_diff_mark wrote it.
+__global__ __launch_bounds__(DIFF_T) void k_co_rank(Pools P, CoIO C, u32 n) {
+  u32 i = blockIdx.x;
+  if (i >= n) return;
+  u32 d = C.docs[i], v = C.version[i], no;
+  if (!co_ok(P, d, v, no)) return;
+  u32 tid = threadIdx.x, l = lane_id(), wv = uni(tid >> 6);
+  const u32 nwv = (v >> 5) + 1u;  // <= pub_words(ord_cap), the bitmap's size
+  const u32* bm = C.bm + C.bm_base[i];
+  u32* rk = C.rk + C.bm_base[i];
+  __shared__ u32 s_w[DIFF_WAVES];
+  u32 carry = 0;
+  for (u32 w0 = 0; w0 < nwv; w0 += DIFF_T * 8u) {
+    u32 wb = w0 + tid * 8u;
+    u32 x[8], c = 0;
+#pragma unroll
+    for (u32 u = 0; u < 8u; u++) {
+      x[u] = wb + u < nwv ? bm[wb + u] : 0u;
+      c += (u32)__popc(x[u]);
+    }
+    u32 incl = wave_incl_scan(c);
+    if (l == 63u) s_w[wv] = incl;
+    __syncthreads();
+    u32 run = carry + incl - c;
+    for (u32 w = 0; w < wv; w++) run += s_w[w];
+#pragma unroll
+    for (u32 u = 0; u < 8u; u++) {
+      if (wb + u < nwv) rk[wb + u] = run;
+      run += (u32)__popc(x[u]);
+    }
+    for (u32 w = 0; w < DIFF_WAVES; w++) carry += s_w[w];
+    __syncthreads();  // (the next pass rewrites the LDS totals)
+  }
+}
+
+// opos and the view's length, one block per index, DIFF_T canonical spans per pass like k_diff.
+__global__ __launch_bounds__(DIFF_T) void k_co_count(Pools P, PubOut O, CoIO C, u32 n) {
+  u32 i = blockIdx.x;
+  if (i >= n) return;
+  u32 d = C.docs[i], v = C.version[i], no;
+  u32 tid = threadIdx.x, l = lane_id(), wv = uni(tid >> 6);
+  if (!co_ok(P, d, v, no)) {
+    if (tid == 0) C.res[i] = CoRes{0u, CO_BAD, no, v, 0ull, 0ull};
+    return;
+  }
+  u64 cb = C.cbase[d], cl = C.clen[d];
+  bool text = cb != NO_CONTENT && cl >= (u64)no;
+  const DocSeg& sg = P.seg[d];
+  const Span* cn = O.canon + sg.canon_base;
+  u32 ns = min(O.canon_n[d], sg.canon_cap);
+  const u32* bm = C.bm + C.bm_base[i];
+  const u32* rk = C.rk + C.bm_base[i];
+  u32* opos = C.opos + C.sp_base[i];
+  __shared__ u32 s_c[DIFF_WAVES];
+  u32 carry = 0;
+  for (u32 k0 = 0; k0 < ns; k0 += DIFF_T) {
+    u32 k = k0 + tid;
+    u32 c = k < ns ? co_span_count(cn[k], v, bm, rk) : 0u;
+    u32 incl = wave_incl_scan(c);
+    if (l == 63u) s_c[wv] = incl;
+    __syncthreads();
+    u32 ex = carry + incl - c;
+    for (u32 w = 0; w < wv; w++) ex += s_c[w];
+    if (k < ns) opos[k] = ex;
+    for (u32 w = 0; w < DIFF_WAVES; w++) carry += s_c[w];
+    __syncthreads();
+  }
+  if (tid == 0) C.res[i] = CoRes{carry, text ? CO_TEXT : 0u, no, v, 0ull, 0ull};
+}
+
+// Exclusive scan of the views' lengths into their offsets (one block; thread t takes a contiguous
+// slice of the indexes); *total = items of all views.
+__global__ __launch_bounds__(DIFF_SCAN_T) void k_co_scan(CoRes* res, u32 n, u64* total) {
+  __shared__ u64 s_a[DIFF_SCAN_T];
+  u32 t = threadIdx.x;
+  u32 per = (n + DIFF_SCAN_T - 1u) / DIFF_SCAN_T;
+  u64 lo = min((u64)t * per, (u64)n), hi = min(lo + per, (u64)n);
+  u64 a = 0;
+  for (u64 k = lo; k < hi; k++) a += res[k].len;  // (0 for an index without a result)
+  s_a[t] = a;
+  __syncthreads();
+  if (t == 0) {
+    a = 0;
+    for (u32 x = 0; x < DIFF_SCAN_T; x++) {
+      u64 p = s_a[x];
+      s_a[x] = a;
+      a += p;
+    }
+    *total = a;
+  }
+  __syncthreads();
+  a = s_a[t];
+  for (u64 k = lo; k < hi; k++) {
+    res[k].off = a;
+    a += res[k].len;
+  }
+}
+
+// The views' items.  One block of CO_WAVES waves per index; wave w takes chunks w, w + CO_WAVES,
+// ... of 64 canonical spans (a chunk's items start at opos[k0], so chunks are independent, and
+// opos[k + 1] - opos[k0] is the chunk's inclusive scan: no recount).  Lane l takes item t + l of
+// the chunk: its span by a 6-step search over the scan, as k_diff's inserted items; inside a
+// span with no marked item below v -- every visible span, and a span deleted only after v -- the
+// order is the span's first plus the item's offset; inside a deleted span that v cuts (some
+// items marked), the j-th clear bit through the rank directory (binary search over the span's
+// words) and a select within the word.  Stores of ord / text are contiguous either way.
+__global__ __launch_bounds__(64 * CO_WAVES) void k_co_write(Pools P, PubOut O, CoIO C, u32 n) {
+  u32 i = blockIdx.x;
+  if (i >= n) return;
+  const CoRes rs = C.res[i];
+  if (rs.flags & CO_BAD) return;
+  u32 d = C.docs[i], v = rs.at, len = rs.len;
+  u32 l = lane_id(), wv = uni(threadIdx.x >> 6);
+  bool text = (rs.flags & CO_TEXT) != 0u;
+  const DocSeg& sg = P.seg[d];
+  const Span* cn = O.canon + sg.canon_base;
+  u32 ns = min(O.canon_n[d], sg.canon_cap);
+  const u32* bm = C.bm + C.bm_base[i];
+  const u32* rk = C.rk + C.bm_base[i];
+  const u32* opos = C.opos + C.sp_base[i];
+  const u32* src = C.content + (text ? C.cbase[d] : 0ull);
+  u32* ord = C.ord + rs.off;
+  u32* txt = C.text + rs.off;
+  __shared__ u64 s_h[CO_WAVES];
+  u64 h = 0;
+  for (u32 k0 = wv * 64u; k0 < ns; k0 += 64u * CO_WAVES) {
+    u32 k = k0 + l;
+    Span sp = k < ns ? cn[k] : Span{0, 0, 0, 0};
+    u32 st = k < ns ? opos[k] : len;            // items before span k
+    u32 nx = k + 1u < ns ? opos[k + 1u] : len;  // ... and before the next one
+    u32 base = rdlane(st, 0);
+    u32 cnt = nx - st, Pi = nx - base, Tn = rdlane(Pi, 63);
+    st -= base;
+    u32 below = sp.order < v ? min(slen(sp), v - sp.order) : 0u;
+    bool cut = cnt != below && cnt != 0u;  // a deleted span with marked and unmarked items below v
+    u32 c0 = cut ? sp.order - co_set_below(bm, rk, sp.order) : 0u;  // clear bits before the span
+    u32 wl = sp.order >> 5, wh = cut ? (sp.order + below - 1u) >> 5 : 0u;
+    for (u32 t = 0; t < Tn; t += 64u) {
+      u32 j = t + l;
+      u32 s = 0;
+#pragma unroll
+      for (u32 step = 32u; step >= 1u; step >>= 1) s += shfl(Pi, s + step - 1u) <= j ? step : 0u;
+      u32 r = j - shfl(st, s);
+      u32 o = shfl(sp.order, s) + r;
+      u32 scut = shfl((u32)cut, s), sc0 = shfl(c0, s), lo = shfl(wl, s), hi = shfl(wh, s);
+      if (j < Tn && scut) {
+        u32 target = sc0 + r;  // clear bits before the wanted item
+        while (lo < hi) {      // the last word with at most `target` clear bits before it
+          u32 mid = (lo + hi + 1u) >> 1;
+          if (32u * mid - rk[mid] <= target) lo = mid;
+          else hi = mid - 1u;
+        }
+        o = min(32u * lo + select32(~bm[lo], target - (32u * lo - rk[lo])), v - 1u);  // (v > 0 here; in range by construction)
+      }
+      u32 x = base + j;
+      if (j < Tn && x < len) {
+        ord[x] = o;
+        if (text) {
+          u32 cp = src[o];
+          txt[x] = cp;
+          h += text_hash(x, cp);
+        }
+      }
+    }
+  }
+  h = wave_sum64(h);
+  if (l == 0) s_h[wv] = h;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 hs = 0;
+    for (u32 w = 0; w < CO_WAVES; w++) hs += s_h[w];
+    C.res[i].digest = text ? mix64(hs ^ ((u64)len << 32 | 0x54ull)) : 0ull;
+  }
+}
+
+// pos -> loc on the view (thread per query): the item's order from the view's order array, then
+// client_with_order as k_pos_to_loc.
+__global__ void k_pos_to_loc_at(Pools P, CoIO C, u32 n_idx, u64 nq, const u32* idx, const u32* pos, u16* agent, u32* seq) {
+  for (u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (u64)gridDim.x * blockDim.x) {
+    u32 i = idx[q], p = pos[q];
+    u16 a = 0xFFFF;
+    u32 sq = INVALID;
+    if (i < n_idx) {
+      CoRes rs = C.res[i];
+      if (!(rs.flags & CO_BAD) && p < rs.len) {
+        u32 d = C.docs[i];
+        u32 order = C.ord[rs.off + p];
+        DocSeg seg = P.seg[d];
+        const CwoRun* cw = P.cwo + seg.cwo_base;
+        i32 r = find_run(cw, P.st[d].n_cwo, order);
+        if (r >= 0) { a = (u16)cw[r].agent; sq = cw[r].seq + (order - cw[r].key); }
+      }
+    }
+    agent[q] = a;
+    seq[q] = sq;
+  }
+}
+
+// loc -> pos on the view (thread per query): (agent, seq) -> order as k_loc_to_pos; an order at
+// or above v does not exist at v (2, like an unknown id); else the span through the published
+// order -> span index, opos and the old-visible items of the span before the order.
+__global__ void k_loc_to_pos_at(Pools P, PubOut O, CoIO C, u32 n_idx, u64 nq, const u32* idx, const u16* agent, const u32* seq,
+                                u32* pos, u8* deleted) {
+  for (u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (u64)gridDim.x * blockDim.x) {
+    u32 i = idx[q];
+    u32 ps = INVALID;
+    u8 dl = 2;
+    if (i < n_idx) {
+      CoRes rs = C.res[i];
+      u32 d = C.docs[i];
+      if (!(rs.flags & CO_BAD) && agent[q] < P.st[d].n_agents) {
+        DocSeg seg = P.seg[d];
+        AgentRec A = P.agents[seg.agent_base + agent[q]];
+        const ARun* ar = P.arun + seg.arun_base + A.run_base;
+        i32 r = find_run(ar, A.run_cnt, seq[q]);
+        if (r >= 0) {
+          u32 order = ar[r].order + (seq[q] - ar[r].key);
+          u32 k = order < rs.at ? span_of_order(O, seg, min(O.canon_n[d], seg.canon_cap), order) : INVALID;
+          if (k != INVALID) {
+            Span sp = O.canon[seg.canon_base + k];
+            ps = C.opos[C.sp_base[i] + k] + (order - sp.order);
+            dl = 0;
+            if (sp.len < 0) {
+              const u32* bm = C.bm + C.bm_base[i];
+              const u32* rk = C.rk + C.bm_base[i];
+              ps -= co_set_below(bm, rk, order) - co_set_below(bm, rk, sp.order);
+              dl = (u8)((bm[order >> 5] >> (order & 31u)) & 1u);
+            }
           }
         }
       }
