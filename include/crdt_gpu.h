@@ -257,6 +257,35 @@ int crdt_loc_to_pos_at_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx
                                  const uint32_t* seq, uint32_t* pos, uint8_t* deleted);
 int crdt_last_checkout_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
 
+/* ---- who wrote what: per-document authorship runs -------------------------------------------
+ * No reference counterpart (print_stats is the nearest thing).  Walk the visible items of a
+ * document's current state in document order (the items of the canonical spans with len > 0);
+ * item number p of that walk is position p, and its id (agent, seq) is what crdt_pos_to_loc
+ * answers for p.  A run is a maximal stretch of consecutive positions whose neighbours chain:
+ * with CRDT_BLAME_AGENT when they have the same agent, with CRDT_BLAME_ID when they have the same
+ * agent and the right one's seq is the left one's plus 1.  agent and seq of a run are those of
+ * its first item: in ID mode item pos + j has id (agent, seq + j), so the runs are the whole
+ * pos -> loc table, run-length encoded.  Runs come in position order and their lens sum to the
+ * document's length; an empty or fully deleted document has none.  Deleted items are not part of
+ * the walk: two visible stretches with tombstones between them chain if their ids allow it. */
+enum { CRDT_BLAME_AGENT = 0, CRDT_BLAME_ID = 1 };
+typedef struct { uint32_t pos, len, agent, seq; } crdt_blame_run;
+/* Compute, on the device and stream-ordered, the runs of docs[i] (publishes first if needed, like
+ * crdt_materialize_async).  docs has no duplicates; an unknown mode is CRDT_E_ARG.  Replaces the
+ * previous blame result; changes no document and neither the diff result nor the checkout.  (The
+ * call waits once inside, for the total that sizes the result array.)  CRDT_E_NOMEM if an
+ * allocation fails: the engine stays usable, without a blame result. */
+int crdt_blame_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, int mode);
+/* Runs per docs[i] of the last blame (syncs).  An index whose document is poisoned has no result:
+ * its count is 0xFFFFFFFF and crdt_blame_read of it returns CRDT_E_ARG; the other indexes are not
+ * affected. */
+int crdt_blame_counts(crdt_engine* e, uint32_t* n_runs);
+/* Result i of the last blame: runs[n_runs[i]].  CRDT_E_ARG for i out of range or before any
+ * blame.  The array is a copy: it stays readable until the next blame or crdt_docs_alloc,
+ * whatever happens to the documents. */
+int crdt_blame_read(crdt_engine* e, uint64_t i, crdt_blame_run* runs);
+int crdt_last_blame_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
+
 /* ListCRDT::len (doc.rs:484-486) */
 int crdt_doc_len(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* len);
 int crdt_doc_status(crdt_engine* e, int32_t* status /* n_docs */);

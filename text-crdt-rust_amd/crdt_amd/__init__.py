@@ -293,6 +293,10 @@ def lib():
     L.crdt_pos_to_loc_at_dev_async.argtypes = [vp, u64, vp, vp, vp, vp]
     L.crdt_loc_to_pos_at_dev_async.argtypes = [vp, u64, vp, vp, vp, vp, vp]
     L.crdt_last_checkout_ms.argtypes = [vp, P(C.c_double)]
+    L.crdt_blame_async.argtypes = [vp, u64, P(u32), C.c_int]
+    L.crdt_blame_counts.argtypes = [vp, P(u32)]
+    L.crdt_blame_read.argtypes = [vp, u64, vp]
+    L.crdt_last_blame_ms.argtypes = [vp, P(C.c_double)]
     L.crdt_last_error.restype = C.c_char_p
     L.crdt_trace_load.argtypes = [C.c_char_p, P(vp)]
     L.crdt_trace_parse.argtypes = [C.c_char_p, u64, P(vp)]
@@ -317,6 +321,7 @@ EXPORTED_SYMBOLS = [
     "crdt_doc_version", "crdt_diff_async", "crdt_diff_counts", "crdt_diff_read", "crdt_last_diff_ms",
     "crdt_checkout_async", "crdt_checkout_lens", "crdt_checkout_read", "crdt_checkout_digest", "crdt_pos_to_loc_at",
     "crdt_loc_to_pos_at", "crdt_pos_to_loc_at_dev_async", "crdt_loc_to_pos_at_dev_async", "crdt_last_checkout_ms",
+    "crdt_blame_async", "crdt_blame_counts", "crdt_blame_read", "crdt_last_blame_ms",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -782,6 +787,52 @@ class Engine:
         _check(self.L.crdt_last_checkout_ms(self.h, C.byref(x)), "last_checkout_ms")
         return x.value
 
+    # --- who wrote what: authorship runs of the current text (crdt_gpu.h "who wrote what")
+    BLAME_MODES = {"agent": 0, "id": 1}
+
+    def blame_async(self, docs, mode):
+        """compute the authorship runs of docs[i] (no duplicates) on the device; mode is "agent" / "id"
+        (or CRDT_BLAME_AGENT = 0 / CRDT_BLAME_ID = 1); replaces the last blame"""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        if d.ndim != 1:
+            raise ValueError("blame: docs is 1-d")
+        _check(self.L.crdt_blame_async(self.h, d.shape[0], _p(d), int(self.BLAME_MODES.get(mode, mode))), "blame_async")
+        self._blame_n = d.shape[0]
+
+    def blame_counts(self) -> np.ndarray:
+        """runs per index of the last blame_async; 0xFFFFFFFF marks an index without a result (a
+        poisoned document)"""
+        out = np.zeros(getattr(self, "_blame_n", 0), np.uint32)
+        _check(self.L.crdt_blame_counts(self.h, _p(out)), "blame_counts")
+        return out
+
+    def blame_read(self, i: int, counts=None) -> np.ndarray:
+        """result i of the last blame_async: runs [n, 4] u32 = (pos, len, agent, seq); raises CrdtError
+        (rc=-100) for an index without a result"""
+        counts = counts if counts is not None else self.blame_counts()
+        bad = not 0 <= i < len(counts) or int(counts[i]) == 0xFFFFFFFF  # (the library answers CRDT_E_ARG)
+        runs = np.zeros((0 if bad else int(counts[i]), 4), np.uint32)
+        _check(self.L.crdt_blame_read(self.h, i, runs.ctypes.data), "blame_read")
+        return runs
+
+    def blame(self, docs, mode="agent", strict: bool = True):
+        """[runs (n, 4) u32 = (pos, len, agent, seq)] per docs[i]: maximal stretches of the current text
+        by one agent (mode="agent"), or with consecutive ids (mode="id": item pos + j of a run is
+        (agent, seq + j)).  An index without a result (a poisoned document) raises CrdtError, or is
+        None with strict=False; the other indexes are not affected."""
+        self.blame_async(docs, mode)
+        counts = self.blame_counts()
+        bad = np.flatnonzero(counts == 0xFFFFFFFF)
+        if strict and bad.size:
+            raise CrdtError(f"blame failed rc=-100 for indexes {bad.tolist()}: a poisoned document")
+        return [None if int(counts[i]) == 0xFFFFFFFF else self.blame_read(i, counts) for i in range(len(counts))]
+
+    def blame_ms(self) -> float:
+        """device time of the last blame (HIP events)"""
+        x = C.c_double()
+        _check(self.L.crdt_last_blame_ms(self.h, C.byref(x)), "last_blame_ms")
+        return x.value
+
     def timings(self):
         a, b = C.c_double(), C.c_double()
         self.L.crdt_last_timings(self.h, C.byref(a), C.byref(b))
@@ -840,6 +891,10 @@ class ListCRDT:
     def to_string_at(self, v: int) -> str:
         from .traces import utf32_to_str
         return utf32_to_str(self.text_at(v))
+
+    def blame(self, mode: str = "agent") -> np.ndarray:
+        """authorship runs [n, 4] u32 = (pos, len, agent, seq) of the current text (Engine.blame)"""
+        return self.e.blame([0], mode)[0]
 
     def status(self) -> int:
         return int(self.e.status()[0])

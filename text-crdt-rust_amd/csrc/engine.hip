@@ -306,6 +306,20 @@ struct crdt_engine {
   bool co_pulled = false;  // ... and co_res_h / last_co_ms hold it
   double last_co_ms = 0;
   u64 pub_epoch = 0, co_epoch = 0;
+  // authorship runs (crdt_blame_async): buffers of its own, kept and grown from call to call like
+  // the diff's; the result array is a copy and stays readable
+  hipEvent_t ev_blame[2] = {nullptr, nullptr};
+  std::vector<u32> blame_docs_h;
+  std::vector<BlameRes> blame_res_h;
+  u32* blame_docs = nullptr;
+  BlameRes* blame_res = nullptr;
+  u64* blame_tot = nullptr;
+  BlameRun* blame_runs = nullptr;
+  u64 blame_n_cap = 0, blame_run_cap = 0;
+  u64 blame_n = 0;
+  bool blame_valid = false;   // a blame result exists (crdt_blame_async succeeded since the last crdt_docs_alloc)
+  bool blame_pulled = false;  // ... and blame_res_h / last_blame_ms hold it
+  double last_blame_ms = 0;
 
   Pools pools_view(const PoolSet& ps) const {
     Pools p{};
@@ -379,6 +393,10 @@ struct crdt_engine {
     co_n_cap = co_bm_cap = co_rk_cap = co_opos_cap = co_out_cap = 0;
     co_n = 0;
     co_valid = co_pulled = false;
+    dfree(blame_docs); dfree(blame_res); dfree(blame_tot); dfree(blame_runs);
+    blame_n_cap = blame_run_cap = 0;
+    blame_n = 0;
+    blame_valid = blame_pulled = false;
   }
 
   int set_device() {
@@ -1532,7 +1550,79 @@ struct crdt_engine {
   }
   // the _at queries' precondition: a checkout whose published index is still the current one
   bool co_fresh() const { return co_valid && published && co_epoch == pub_epoch; }
+
+  BlameIO blame_view() const {
+    BlameIO io{};
+    io.docs = blame_docs;
+    io.res = blame_res;
+    io.runs = blame_runs;
+    return io;
+  }
+  // crdt_blame_async: count every listed document's runs, scan the counts into offsets on the
+  // device, size the result array from the total (the one host read between the sweeps: 8 bytes),
+  // write the runs.
+  int blame(u64 n, const uint32_t* dl, u32 mode) {
+    int r = set_device();
+    if (r) return r;
+    blame_valid = blame_pulled = false;
+    if (!published) {
+      r = publish();
+      if (r) return r;
+    }
+    blame_n = n;
+    if (!n) {
+      blame_valid = true;
+      return 0;
+    }
+    blame_docs_h.assign(dl, dl + n);
+    if (n > blame_n_cap) {
+      HIPCHK(hipStreamSynchronize(stream));
+      dfree(blame_docs); dfree(blame_res);
+      blame_n_cap = 0;
+      HIPCHK(dalloc(blame_docs, n));
+      HIPCHK(dalloc(blame_res, n));
+      blame_n_cap = n;
+    }
+    if (!blame_tot) HIPCHK(dalloc(blame_tot, 1));
+    HIPCHK(hipMemcpyAsync(blame_docs, blame_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(ev_blame[0], stream));
+    Pools pv = pools_view(pools);
+    PubOut ov = pub_view();
+    hipLaunchKernelGGL(k_blame<false>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, blame_view(), (u32)n, mode);
+    hipLaunchKernelGGL(k_blame_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, blame_res, (u32)n, blame_tot);
+    HIPCHK(hipGetLastError());
+    u64 tot = 0;
+    HIPCHK(hipMemcpyAsync(&tot, blame_tot, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    r = diff_grow(blame_runs, blame_run_cap, tot);
+    if (r) return r;
+    hipLaunchKernelGGL(k_blame<true>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, blame_view(), (u32)n, mode);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev_blame[1], stream));
+    blame_valid = true;
+    return 0;
+  }
+  // the per-index results and the device time of the last blame, on the host (waits for it)
+  int blame_finish() {
+    if (!blame_valid) return CRDT_E_ARG;
+    if (blame_pulled) return 0;
+    int r = set_device();
+    if (r) return r;
+    blame_res_h.resize(blame_n);
+    last_blame_ms = 0;
+    if (blame_n) {
+      HIPCHK(hipMemcpyAsync(blame_res_h.data(), blame_res, blame_n * sizeof(BlameRes), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, ev_blame[0], ev_blame[1]);
+      last_blame_ms = ms;
+    }
+    blame_pulled = true;
+    return 0;
+  }
 };
+static_assert(sizeof(BlameRun) == sizeof(crdt_blame_run) && sizeof(crdt_blame_run) == 16, "crdt_blame_run is the kernels' BlameRun");
+static_assert(BLAME_AGENT == CRDT_BLAME_AGENT && BLAME_ID == CRDT_BLAME_ID, "CRDT_BLAME_* are the kernels' modes");
 static_assert(sizeof(Patch) == sizeof(crdt_patch) && sizeof(crdt_patch) == 16, "crdt_patch is the kernels' Patch");
 
 static bool valid(const crdt_engine* e) { return e && e->n_docs > 0; }
@@ -1591,6 +1681,8 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   for (auto& x : e->ev_co)
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
+  for (auto& x : e->ev_blame)
+    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   *out = e.release();
   return 0;
 }
@@ -1605,6 +1697,8 @@ void crdt_engine_destroy(crdt_engine* e) {
   for (auto& x : e->ev_diff)
     if (x) (void)hipEventDestroy(x);
   for (auto& x : e->ev_co)
+    if (x) (void)hipEventDestroy(x);
+  for (auto& x : e->ev_blame)
     if (x) (void)hipEventDestroy(x);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -2329,6 +2423,7 @@ uint64_t crdt_mem_bytes(const crdt_engine* e) {
          e->diff_n_cap * (4 + 4 + 8 + sizeof(DiffRes)) +
          (e->co_bm_cap + e->co_rk_cap + e->co_opos_cap + 2 * e->co_out_cap) * 4 +
          e->co_n_cap * (4 + 4 + 8 + 8 + sizeof(CoRes)) +
+         e->blame_run_cap * sizeof(BlameRun) + e->blame_n_cap * (4 + sizeof(BlameRes)) +
          e->n_docs * (sizeof(DocState) + sizeof(DocSeg) + 4 + 4 + 8);
 }
 
@@ -2521,6 +2616,54 @@ int crdt_last_checkout_ms(crdt_engine* e, double* ms) {
     if (r) return r;
   }
   *ms = e->last_co_ms;
+  return 0;
+}
+
+int crdt_blame_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, int mode) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n_docs && !docs) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
+  if (mode != CRDT_BLAME_AGENT && mode != CRDT_BLAME_ID) {
+    g_last_error = "blame: mode is CRDT_BLAME_AGENT or CRDT_BLAME_ID";
+    return CRDT_E_ARG;
+  }
+  g_alloc_oom = false;
+  int r = e->blame(n_docs, docs, (u32)mode);
+  // (no relayout is involved: an allocation that fails leaves the engine as it was, without a blame result)
+  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
+  return r;
+}
+
+int crdt_blame_counts(crdt_engine* e, uint32_t* n_runs) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->blame_finish();
+  if (r) return r;
+  for (u64 i = 0; n_runs && i < e->blame_n; i++) n_runs[i] = (e->blame_res_h[i].flags & BLAME_BAD) ? INVALID : e->blame_res_h[i].n_runs;
+  return 0;
+}
+
+int crdt_blame_read(crdt_engine* e, uint64_t i, crdt_blame_run* runs) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->blame_finish();
+  if (r) return r;
+  if (i >= e->blame_n) return CRDT_E_ARG;
+  const BlameRes& x = e->blame_res_h[i];
+  if (x.flags & BLAME_BAD) {
+    g_last_error = "blame: a poisoned document";
+    return CRDT_E_ARG;
+  }
+  if (runs && x.n_runs) HIPCHK(hipMemcpy(runs, e->blame_runs + x.off, (u64)x.n_runs * sizeof(BlameRun), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int crdt_last_blame_ms(crdt_engine* e, double* ms) {
+  if (!e || !ms) return CRDT_E_ARG;
+  if (e->blame_valid && !e->blame_pulled) {
+    int r = e->blame_finish();
+    if (r) return r;
+  }
+  *ms = e->last_blame_ms;
   return 0;
 }
 

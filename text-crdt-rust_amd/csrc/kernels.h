@@ -12,6 +12,8 @@
 //   k_co_rank / k_co_count / k_co_scan / k_co_write  the document at a past version (checkout): its
 //               items' orders and text, from the same inputs (block per listed document)
 //   k_pos_to_loc_at / k_loc_to_pos_at   the two lookups on a checked-out view (thread per query)
+//   k_blame / k_blame_scan  authorship runs of the current text, from the published index +
+//               client_with_order (block per listed document)
 #pragma once
 #include "replay_core.h"
 #include "wave_gpu.h"
@@ -1863,6 +1865,183 @@ __global__ void k_loc_to_pos_at(Pools P, PubOut O, CoIO C, u32 n_idx, u64 nq, co
     }
     pos[q] = ps;
     deleted[q] = dl;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Authorship runs (crdt_blame_async): who wrote each part of a document's current text, from the
+// published index and client_with_order.  No reference counterpart (print_stats is the nearest).
+// Walk the visible items in document order (the canonical spans with len > 0, item by item); item
+// p has an order and through client_with_order an id (agent, seq), what k_pos_to_loc answers for
+// p.  A run is a maximal stretch of positions whose neighbours chain: same agent (BLAME_AGENT),
+// or same agent and seq + 1 (BLAME_ID).  A run is {pos, len, agent, seq} of its first item.
+//
+// Per visible canonical span [o, o + len) the orders are dense, so the client_with_order runs
+// that overlap it are consecutive table entries from find_run(o): every boundary between two of
+// them inside the span starts a run unless the two chain (compared, the table need not be
+// maximally coalesced), and the span's first item starts one unless it chains with the tail --
+// (agent, next seq) -- of the last visible span before it, tombstones in between or not.
+// ---------------------------------------------------------------------------------------------
+struct BlameRun { u32 pos, len, agent, seq; };  // crdt_blame_run (include/crdt_gpu.h)
+constexpr u32 BLAME_AGENT = 0u, BLAME_ID = 1u;  // CRDT_BLAME_*
+constexpr u32 BLAME_BAD = 1u;                   // a poisoned document: no result for this index
+struct BlameRes {
+  u32 n_runs, flags;
+  u64 off;  // first run of this index in the result array (k_blame_scan)
+};
+struct BlameIO {
+  const u32* docs;  // [i] the listed documents
+  BlameRes* res;    // [i]
+  BlameRun* runs;   // [res[i].off + p]
+};
+
+// The client_with_order runs under one visible canonical span of ln items whose first order lies
+// in run r0: the id of its first item (ha, hs), the tail after its last one (ta, ts) and the
+// number of run starts inside it.  STORE writes those starts to out[p], out[p + 1], ... (below
+// lim only).  A serial walk: one table entry per step, however many the span covers.
+template <bool STORE>
+__device__ __forceinline__ u32 blame_walk(const CwoRun* cw, u32 ncwo, u32 r0, u32 order, u32 ln, u32 mode, u32& ha, u32& hs,
+                                          u32& ta, u32& ts, BlameRun* out, u32 p, u32 lim, u32 pos) {
+  CwoRun q = cw[r0];
+  u32 off = order - q.key;
+  ha = q.agent;
+  hs = q.seq + off;
+  u32 done = min(q.len - off, ln);
+  ta = ha;
+  ts = hs + done;
+  u32 starts = 0;
+  for (u32 r = r0 + 1u; done < ln && r < ncwo; r++) {
+    q = cw[r];
+    bool chain = (q.agent == ta) & ((mode == BLAME_AGENT) | (q.seq == ts));
+    if (!chain) {
+      if (STORE && p + starts < lim) out[p + starts] = BlameRun{pos + done, 0u, q.agent, q.seq};
+      starts++;
+    }
+    u32 take = min(q.len, ln - done);
+    ta = q.agent;
+    ts = q.seq + take;
+    done += take;
+  }
+  return starts;
+}
+
+// One block per listed document, DIFF_T canonical spans per loop pass, in document order, like
+// k_diff.  WRITE = false counts the document's runs (res[i]); WRITE = true, after k_blame_scan,
+// writes them.  Each thread walks its span (blame_walk).  The tail of the last visible span
+// before it comes from the same wave (the highest visible lane below this one: a ballot and a
+// shuffle), from an earlier wave of the pass (LDS) or from an earlier pass (carried in registers:
+// every thread folds the same LDS values, as k_diff's c_open).  A wave scan of the spans' start
+// counts gives each span the index of its first run.  The start of run p writes {pos, 0, agent,
+// seq}; a last sweep over the document's runs turns neighbouring pos values into len.
+template <bool WRITE>
+__global__ __launch_bounds__(DIFF_T) void k_blame(Pools P, PubOut O, BlameIO B, u32 n, u32 mode) {
+  u32 i = blockIdx.x;
+  if (i >= n) return;
+  u32 d = B.docs[i];
+  u32 tid = threadIdx.x, l = lane_id(), wv = uni(tid >> 6);
+  i32 stt = P.st[d].status;
+  if (stt != ST_OK && stt != ST_NEED_CAPACITY) {
+    if (!WRITE && tid == 0) B.res[i] = BlameRes{0u, BLAME_BAD, 0ull};
+    return;
+  }
+  const DocSeg& sg = P.seg[d];
+  const Span* cn = O.canon + sg.canon_base;
+  const u32* vp = O.vpos + sg.canon_base;
+  u32 ns = min(O.canon_n[d], sg.canon_cap);
+  const CwoRun* cw = P.cwo + sg.cwo_base;
+  u32 ncwo = min(P.st[d].n_cwo, sg.cwo_cap);
+  u32 my_runs = 0;  // (WRITE) this index's count from the first sweep: every store stays below it
+  BlameRun* runs = nullptr;
+  if (WRITE) {
+    BlameRes rs = B.res[i];
+    my_runs = rs.n_runs;
+    runs = B.runs + rs.off;
+  }
+  __shared__ u32 s_has[DIFF_WAVES], s_ta[DIFF_WAVES], s_ts[DIFF_WAVES], s_c[DIFF_WAVES];
+  u32 c_has = 0, c_ta = 0, c_ts = 0, c_runs = 0;  // carried: a visible item was seen, its tail; runs so far
+  for (u32 k0 = 0; k0 < ns; k0 += DIFF_T) {
+    u32 k = k0 + tid;
+    Span sp = k < ns ? cn[k] : Span{0, 0, 0, 0};
+    bool vis = sp.len > 0;
+    u32 ln = vis ? (u32)sp.len : 0u;
+    u32 pos = vis ? vp[k] : 0u;
+    i32 r0 = vis ? find_run(cw, ncwo, sp.order) : -1;
+    // (an order outside the table -- never in a healthy document -- is one piece with the id
+    // k_pos_to_loc answers for it)
+    u32 ha = 0xFFFFu, hs = INVALID, ta = 0xFFFFu, ts = INVALID, inner = 0;
+    if (r0 >= 0) inner = blame_walk<false>(cw, ncwo, (u32)r0, sp.order, ln, mode, ha, hs, ta, ts, nullptr, 0u, 0u, pos);
+    u64 mV = ballot(vis);
+    u32 top = mV ? 63u - (u32)__builtin_clzll(mV) : 0u;
+    if (l == top) {  // the wave's last visible span (lane 0 of a wave without one)
+      s_has[wv] = mV != 0ull;
+      s_ta[wv] = ta;
+      s_ts[wv] = ts;
+    }
+    __syncthreads();
+    u32 p_has = c_has, p_ta = c_ta, p_ts = c_ts;
+    for (u32 w = 0; w < wv; w++)
+      if (s_has[w]) { p_has = 1u; p_ta = s_ta[w]; p_ts = s_ts[w]; }
+    u64 below = mV & ((1ull << l) - 1ull);
+    u32 src = below ? 63u - (u32)__builtin_clzll(below) : l;
+    u32 qa = shfl(ta, src), qs = shfl(ts, src);
+    if (below) { p_has = 1u; p_ta = qa; p_ts = qs; }
+    bool chained = (p_has != 0u) & (p_ta == ha) & ((mode == BLAME_AGENT) | (p_ts == hs));
+    bool hstart = vis && !chained;  // (the document's first visible item always starts a run)
+    u32 cnt = (u32)hstart + inner;
+    u32 Ci = wave_incl_scan(cnt);
+    if (l == 63u) s_c[wv] = Ci;
+    __syncthreads();
+    if (WRITE) {
+      u32 p = c_runs + Ci - cnt;
+      for (u32 w = 0; w < wv; w++) p += s_c[w];
+      if (hstart && p < my_runs) runs[p] = BlameRun{pos, 0u, ha, hs};
+      if (inner) blame_walk<true>(cw, ncwo, (u32)r0, sp.order, ln, mode, ha, hs, ta, ts, runs, p + (u32)hstart, my_runs, pos);
+    }
+    for (u32 w = 0; w < DIFF_WAVES; w++) {
+      if (s_has[w]) { c_has = 1u; c_ta = s_ta[w]; c_ts = s_ts[w]; }
+      c_runs += s_c[w];
+    }
+    __syncthreads();  // (the next pass rewrites the LDS values)
+  }
+  if (!WRITE) {
+    if (tid == 0) B.res[i] = BlameRes{c_runs, 0u, 0ull};
+    return;
+  }
+  // len of run p: from its pos to the next run's (the document's length after the last one)
+  u32 nr = min(c_runs, my_runs);
+  u32 dlen = ns ? vp[ns - 1u] + clen(cn[ns - 1u]) : 0u;
+  __syncthreads();
+  for (u32 p = tid; p < nr; p += DIFF_T) {
+    u32 nx = p + 1u < nr ? runs[p + 1u].pos : dlen;
+    runs[p].len = nx - runs[p].pos;
+  }
+}
+
+// Exclusive scan of the indexes' run counts into their offsets (k_co_scan's shape); *total = runs
+// of all indexes.
+__global__ __launch_bounds__(DIFF_SCAN_T) void k_blame_scan(BlameRes* res, u32 n, u64* total) {
+  __shared__ u64 s_a[DIFF_SCAN_T];
+  u32 t = threadIdx.x;
+  u32 per = (n + DIFF_SCAN_T - 1u) / DIFF_SCAN_T;
+  u64 lo = min((u64)t * per, (u64)n), hi = min(lo + per, (u64)n);
+  u64 a = 0;
+  for (u64 k = lo; k < hi; k++) a += res[k].n_runs;  // (0 for an index without a result)
+  s_a[t] = a;
+  __syncthreads();
+  if (t == 0) {
+    a = 0;
+    for (u32 x = 0; x < DIFF_SCAN_T; x++) {
+      u64 p = s_a[x];
+      s_a[x] = a;
+      a += p;
+    }
+    *total = a;
+  }
+  __syncthreads();
+  a = s_a[t];
+  for (u64 k = lo; k < hi; k++) {
+    res[k].off = a;
+    a += res[k].n_runs;
   }
 }
 
