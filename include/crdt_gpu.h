@@ -286,6 +286,58 @@ int crdt_blame_counts(crdt_engine* e, uint32_t* n_runs);
 int crdt_blame_read(crdt_engine* e, uint64_t i, crdt_blame_run* runs);
 int crdt_last_blame_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
 
+/* ---- encoded text and unit offsets: UTF-8 / UTF-16 output, unit offset <-> position ----------
+ * ListCRDT::to_string (doc.rs:498-505) returns a Rust String, which is UTF-8; an editor or LSP
+ * client addresses text by UTF-16 code-unit offsets; every position of this header counts chars.
+ * These calls hand over the text of crdt_text in either form and convert offsets both ways, on the
+ * device.
+ *
+ * A content value c is a scalar value iff c < 0xD800 or 0xE000 <= c <= 0x10FFFF; any other value
+ * (a surrogate, or above 0x10FFFF) is encoded as U+FFFD.  CRDT_ENC_UTF8: the unit is a byte, the
+ * width 1 / 2 / 3 / 4 for c below 0x80 / 0x800 / 0x10000 / otherwise, standard bit layout.
+ * CRDT_ENC_UTF16: the unit is a uint16_t in host byte order, the width 1 below 0x10000, otherwise 2:
+ * 0xD800 + ((c - 0x10000) >> 10), then 0xDC00 + ((c - 0x10000) & 0x3FF).  A document's encoded text
+ * is the concatenation of the encodings of its visible items in document order, the items of
+ * crdt_text; chars is their count, units the encoded length in units. */
+enum { CRDT_ENC_UTF8 = 0, CRDT_ENC_UTF16 = 1 };
+/* Encode, on the device and stream-ordered, the text of docs[i] (materialises first if needed, and
+ * therefore publishes).  docs has no duplicates; an unknown enc is CRDT_E_ARG.  Replaces the
+ * previous encode result; changes no document and none of the diff result, the checkout and the
+ * blame result.  (The call waits once inside, for the total that sizes the unit array.)
+ * CRDT_E_NOMEM if an allocation fails: the engine stays usable, without an encode result. */
+int crdt_encode_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, int enc);
+/* Units and chars per docs[i] of the last encode (syncs; either pointer may be NULL).  An index
+ * whose document is poisoned, has no content or too short a content stream has no result: both are
+ * 0xFFFFFFFF, crdt_encode_read of it and a host-form query that names it return CRDT_E_ARG; the
+ * other indexes are not affected.  A document whose units would not fit below 0xFFFFFFFF has no
+ * result either. */
+int crdt_encode_lens(crdt_engine* e, uint32_t* units, uint32_t* chars);
+/* Result i of the last encode: units[i] units (bytes, or uint16_t) into out; cap_units >= units[i].
+ * CRDT_E_ARG for i out of range or before any encode. */
+int crdt_encode_read(crdt_engine* e, uint64_t i, void* out, uint64_t cap_units);
+/* The two mappings on the last encode's results: idx[q] names an index of it.
+ *   pos -> units: for pos <= chars the units before char pos (pos == chars gives units), else
+ *     0xFFFFFFFF.
+ *   units -> pos: for u < units the char whose encoding covers unit u, with mid = 1 if u is not
+ *     that char's first unit (a continuation byte / a low surrogate), else 0; u == units gives
+ *     chars, mid 0; u > units gives 0xFFFFFFFF, mid 0.  mid may be NULL.
+ * The pos -> units answer of a units -> pos answer is <= u, with equality exactly when mid == 0.
+ * An idx out of range, or one without a result, gives CRDT_E_ARG for the whole call and writes
+ * nothing; so does a query before any encode.  The queries read nothing but the encode result
+ * (the unit array and its index): result and queries stay valid until the next encode or
+ * crdt_docs_alloc, whatever is replayed, published or materialised in between. */
+int crdt_pos_to_units(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, uint32_t* unit);
+int crdt_units_to_pos(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* unit, uint32_t* pos,
+                      uint8_t* mid);
+/* Device-pointer forms (inputs/outputs already in HBM; async on the engine stream).  idx cannot be
+ * checked on the host: a query whose idx is out of range or has no result is answered 0xFFFFFFFF,
+ * with mid = 0. */
+int crdt_pos_to_units_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos,
+                                uint32_t* unit);
+int crdt_units_to_pos_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* unit,
+                                uint32_t* pos, uint8_t* mid);
+int crdt_last_encode_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
+
 /* ListCRDT::len (doc.rs:484-486) */
 int crdt_doc_len(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* len);
 int crdt_doc_status(crdt_engine* e, int32_t* status /* n_docs */);

@@ -297,6 +297,14 @@ def lib():
     L.crdt_blame_counts.argtypes = [vp, P(u32)]
     L.crdt_blame_read.argtypes = [vp, u64, vp]
     L.crdt_last_blame_ms.argtypes = [vp, P(C.c_double)]
+    L.crdt_encode_async.argtypes = [vp, u64, P(u32), C.c_int]
+    L.crdt_encode_lens.argtypes = [vp, P(u32), P(u32)]
+    L.crdt_encode_read.argtypes = [vp, u64, vp, u64]
+    L.crdt_pos_to_units.argtypes = [vp, u64, P(u32), P(u32), P(u32)]
+    L.crdt_units_to_pos.argtypes = [vp, u64, P(u32), P(u32), P(u32), P(C.c_uint8)]
+    L.crdt_pos_to_units_dev_async.argtypes = [vp, u64, vp, vp, vp]
+    L.crdt_units_to_pos_dev_async.argtypes = [vp, u64, vp, vp, vp, vp]
+    L.crdt_last_encode_ms.argtypes = [vp, P(C.c_double)]
     L.crdt_last_error.restype = C.c_char_p
     L.crdt_trace_load.argtypes = [C.c_char_p, P(vp)]
     L.crdt_trace_parse.argtypes = [C.c_char_p, u64, P(vp)]
@@ -322,6 +330,8 @@ EXPORTED_SYMBOLS = [
     "crdt_checkout_async", "crdt_checkout_lens", "crdt_checkout_read", "crdt_checkout_digest", "crdt_pos_to_loc_at",
     "crdt_loc_to_pos_at", "crdt_pos_to_loc_at_dev_async", "crdt_loc_to_pos_at_dev_async", "crdt_last_checkout_ms",
     "crdt_blame_async", "crdt_blame_counts", "crdt_blame_read", "crdt_last_blame_ms",
+    "crdt_encode_async", "crdt_encode_lens", "crdt_encode_read", "crdt_pos_to_units", "crdt_units_to_pos",
+    "crdt_pos_to_units_dev_async", "crdt_units_to_pos_dev_async", "crdt_last_encode_ms",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -833,6 +843,76 @@ class Engine:
         _check(self.L.crdt_last_blame_ms(self.h, C.byref(x)), "last_blame_ms")
         return x.value
 
+    # --- encoded text and unit offsets (crdt_gpu.h "encoded text and unit offsets")
+    ENCODINGS = {"utf8": 0, "utf16": 1}
+
+    def encode_async(self, docs, enc):
+        """encode the text of docs[i] (no duplicates) on the device; enc is "utf8" / "utf16" (or
+        CRDT_ENC_UTF8 = 0 / CRDT_ENC_UTF16 = 1); replaces the last encode"""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        if d.ndim != 1:
+            raise ValueError("encode: docs is 1-d")
+        enc = int(self.ENCODINGS.get(enc, enc))
+        _check(self.L.crdt_encode_async(self.h, d.shape[0], _p(d), enc), "encode_async")
+        self._enc_n, self._enc = d.shape[0], enc
+
+    def encode_lens(self):
+        """(units, chars) per index of the last encode_async; 0xFFFFFFFF marks an index without a
+        result (a poisoned document, one without content or with too short a stream)"""
+        n = getattr(self, "_enc_n", 0)
+        units, chars = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        _check(self.L.crdt_encode_lens(self.h, _p(units), _p(chars)), "encode_lens")
+        return units, chars
+
+    def encode_read(self, i: int, lens=None):
+        """result i of the last encode_async: bytes (UTF-8) or an np.uint16 array (UTF-16); raises
+        CrdtError (rc=-100) for an index without a result"""
+        units = (lens if lens is not None else self.encode_lens())[0]
+        bad = not 0 <= i < len(units) or int(units[i]) == 0xFFFFFFFF  # (the library answers CRDT_E_ARG)
+        n = 0 if bad else int(units[i])
+        out = np.zeros(n, np.uint16 if getattr(self, "_enc", 0) == 1 else np.uint8)
+        _check(self.L.crdt_encode_read(self.h, i, out.ctypes.data, n), "encode_read")
+        return out if out.dtype == np.uint16 else out.tobytes()
+
+    def encode(self, docs, enc="utf8", strict: bool = True):
+        """[bytes (enc="utf8") or np.uint16 array (enc="utf16")] per docs[i]: the document's text,
+        encoded.  An index without a result raises CrdtError, or is None with strict=False; the other
+        indexes are not affected."""
+        self.encode_async(docs, enc)
+        lens = self.encode_lens()
+        bad = np.flatnonzero(lens[0] == 0xFFFFFFFF)
+        if strict and bad.size:
+            raise CrdtError(f"encode failed rc=-100 for indexes {bad.tolist()}: a poisoned document, or one without content")
+        return [None if int(lens[0][i]) == 0xFFFFFFFF else self.encode_read(i, lens) for i in range(len(lens[0]))]
+
+    def pos_to_units(self, idx, pos) -> np.ndarray:
+        """units before char pos[q] of index idx[q] of the last encode (0xFFFFFFFF: pos above its chars)"""
+        i = np.ascontiguousarray(idx, dtype=np.uint32)
+        p = np.ascontiguousarray(pos, dtype=np.uint32)
+        if i.shape != p.shape or i.ndim != 1:
+            raise ValueError("pos_to_units: idx and pos are 1-d and of equal length")
+        u = np.zeros(p.shape[0], np.uint32)
+        _check(self.L.crdt_pos_to_units(self.h, p.shape[0], _p(i), _p(p), _p(u)), "pos_to_units")
+        return u
+
+    def units_to_pos(self, idx, unit):
+        """(pos, mid): the char of index idx[q] of the last encode that covers unit unit[q], and whether
+        the unit is not that char's first (0xFFFFFFFF, 0: unit above its units)"""
+        i = np.ascontiguousarray(idx, dtype=np.uint32)
+        u = np.ascontiguousarray(unit, dtype=np.uint32)
+        if i.shape != u.shape or i.ndim != 1:
+            raise ValueError("units_to_pos: idx and unit are 1-d and of equal length")
+        p = np.zeros(u.shape[0], np.uint32)
+        m = np.zeros(u.shape[0], np.uint8)
+        _check(self.L.crdt_units_to_pos(self.h, u.shape[0], _p(i), _p(u), _p(p), _p(m, C.c_uint8)), "units_to_pos")
+        return p, m
+
+    def encode_ms(self) -> float:
+        """device time of the last encode (HIP events)"""
+        x = C.c_double()
+        _check(self.L.crdt_last_encode_ms(self.h, C.byref(x)), "last_encode_ms")
+        return x.value
+
     def timings(self):
         a, b = C.c_double(), C.c_double()
         self.L.crdt_last_timings(self.h, C.byref(a), C.byref(b))
@@ -895,6 +975,18 @@ class ListCRDT:
     def blame(self, mode: str = "agent") -> np.ndarray:
         """authorship runs [n, 4] u32 = (pos, len, agent, seq) of the current text (Engine.blame)"""
         return self.e.blame([0], mode)[0]
+
+    def to_bytes(self) -> bytes:
+        """the text as UTF-8 (what the reference's to_string holds, doc.rs:498-505), encoded on the device"""
+        return self.e.encode([0], "utf8")[0]
+
+    def len_utf16(self) -> int:
+        """length of the text in UTF-16 code units"""
+        self.e.encode_async([0], "utf16")
+        n = int(self.e.encode_lens()[0][0])
+        if n == 0xFFFFFFFF:
+            raise CrdtError("len_utf16 failed rc=-100: a poisoned document, or one without content")
+        return n
 
     def status(self) -> int:
         return int(self.e.status()[0])

@@ -16,6 +16,7 @@
 #include "crdt_gpu.h"
 #include "host_plan.h"
 #include "kernels.h"
+#include "encode.h"
 
 using namespace crdt;
 
@@ -320,6 +321,25 @@ struct crdt_engine {
   bool blame_valid = false;   // a blame result exists (crdt_blame_async succeeded since the last crdt_docs_alloc)
   bool blame_pulled = false;  // ... and blame_res_h / last_blame_ms hold it
   double last_blame_ms = 0;
+  // encoded text (crdt_encode_async): buffers of its own, kept and grown from call to call like
+  // the diff's.  The unit pool and its index (samples, per-index results) are copies: the queries
+  // read nothing else, so they stay valid whatever happens to the documents.
+  hipEvent_t ev_enc[2] = {nullptr, nullptr};
+  std::vector<u32> enc_docs_h;
+  std::vector<u64> enc_sp_h;
+  std::vector<EncRes> enc_res_h;
+  u32* enc_docs = nullptr;
+  u64* enc_sp_base = nullptr;
+  EncRes* enc_res = nullptr;
+  u64* enc_tot = nullptr;
+  u32* enc_samples = nullptr;
+  u8* enc_units = nullptr;
+  u64 enc_n_cap = 0, enc_sp_cap = 0, enc_unit_cap = 0;  // (enc_unit_cap in bytes)
+  u64 enc_n = 0;
+  u32 enc_mode = 0;
+  bool enc_valid = false;   // an encode result exists (crdt_encode_async succeeded since the last crdt_docs_alloc)
+  bool enc_pulled = false;  // ... and enc_res_h / last_enc_ms hold it
+  double last_enc_ms = 0;
 
   Pools pools_view(const PoolSet& ps) const {
     Pools p{};
@@ -397,6 +417,10 @@ struct crdt_engine {
     blame_n_cap = blame_run_cap = 0;
     blame_n = 0;
     blame_valid = blame_pulled = false;
+    dfree(enc_docs); dfree(enc_sp_base); dfree(enc_res); dfree(enc_tot); dfree(enc_samples); dfree(enc_units);
+    enc_n_cap = enc_sp_cap = enc_unit_cap = 0;
+    enc_n = 0;
+    enc_valid = enc_pulled = false;
   }
 
   int set_device() {
@@ -1620,7 +1644,94 @@ struct crdt_engine {
     blame_pulled = true;
     return 0;
   }
+
+  EncIO enc_view() const {
+    EncIO io{};
+    io.docs = enc_docs;
+    io.sp_base = enc_sp_base;
+    io.res = enc_res;
+    io.samples = enc_samples;
+    io.units = enc_units;
+    return io;
+  }
+  // crdt_encode_async: count every listed document's units (and write its samples), scan the
+  // counts into offsets on the device, size the unit pool from the total (the one host read between
+  // the sweeps: 8 bytes), write the units.
+  int encode(u64 n, const uint32_t* dl, u32 enc) {
+    int r = set_device();
+    if (r) return r;
+    enc_valid = enc_pulled = false;
+    if (!materialized) {
+      r = materialize();
+      if (r) return r;
+    }
+    enc_n = n;
+    enc_mode = enc;
+    if (!n) {
+      enc_valid = true;
+      return 0;
+    }
+    enc_docs_h.assign(dl, dl + n);
+    enc_sp_h.resize(n);
+    u64 n_samples = 0;  // a document of c chars has c / ENC_S + 1 samples, and c <= ord_cap
+    for (u64 i = 0; i < n; i++) {
+      enc_sp_h[i] = n_samples;
+      n_samples += seg_h[dl[i]].ord_cap / ENC_S + 1u;
+    }
+    if (n > enc_n_cap) {
+      HIPCHK(hipStreamSynchronize(stream));
+      dfree(enc_docs); dfree(enc_sp_base); dfree(enc_res);
+      enc_n_cap = 0;
+      HIPCHK(dalloc(enc_docs, n));
+      HIPCHK(dalloc(enc_sp_base, n));
+      HIPCHK(dalloc(enc_res, n));
+      enc_n_cap = n;
+    }
+    if (!enc_tot) HIPCHK(dalloc(enc_tot, 1));
+    r = diff_grow(enc_samples, enc_sp_cap, n_samples);
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(enc_docs, enc_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(enc_sp_base, enc_sp_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(ev_enc[0], stream));
+    Pools pv = pools_view(pools);
+    TextIO tv = text_view();
+    if (enc == ENC_UTF8) hipLaunchKernelGGL(k_enc_count<ENC_UTF8>, dim3((u32)n), dim3(ENC_T), 0, stream, pv, tv, enc_view(), (u32)n);
+    else hipLaunchKernelGGL(k_enc_count<ENC_UTF16>, dim3((u32)n), dim3(ENC_T), 0, stream, pv, tv, enc_view(), (u32)n);
+    hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, enc_res, (u32)n, enc_tot);
+    HIPCHK(hipGetLastError());
+    u64 tot = 0;
+    HIPCHK(hipMemcpyAsync(&tot, enc_tot, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    // (the pool ends on a dword: the queries read it a dword at a time)
+    r = diff_grow(enc_units, enc_unit_cap, (tot * (enc == ENC_UTF8 ? 1u : 2u) + 3u) / 4u * 4u);
+    if (r) return r;
+    if (enc == ENC_UTF8) hipLaunchKernelGGL(k_enc_write<ENC_UTF8>, dim3((u32)n), dim3(ENC_T), 0, stream, pv, tv, enc_view(), (u32)n);
+    else hipLaunchKernelGGL(k_enc_write<ENC_UTF16>, dim3((u32)n), dim3(ENC_T), 0, stream, pv, tv, enc_view(), (u32)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev_enc[1], stream));
+    enc_valid = true;
+    return 0;
+  }
+  // the per-index results and the device time of the last encode, on the host (waits for it)
+  int enc_finish() {
+    if (!enc_valid) return CRDT_E_ARG;
+    if (enc_pulled) return 0;
+    int r = set_device();
+    if (r) return r;
+    enc_res_h.resize(enc_n);
+    last_enc_ms = 0;
+    if (enc_n) {
+      HIPCHK(hipMemcpyAsync(enc_res_h.data(), enc_res, enc_n * sizeof(EncRes), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, ev_enc[0], ev_enc[1]);
+      last_enc_ms = ms;
+    }
+    enc_pulled = true;
+    return 0;
+  }
 };
+static_assert(ENC_UTF8 == CRDT_ENC_UTF8 && ENC_UTF16 == CRDT_ENC_UTF16, "CRDT_ENC_* are the kernels' encodings");
 static_assert(sizeof(BlameRun) == sizeof(crdt_blame_run) && sizeof(crdt_blame_run) == 16, "crdt_blame_run is the kernels' BlameRun");
 static_assert(BLAME_AGENT == CRDT_BLAME_AGENT && BLAME_ID == CRDT_BLAME_ID, "CRDT_BLAME_* are the kernels' modes");
 static_assert(sizeof(Patch) == sizeof(crdt_patch) && sizeof(crdt_patch) == 16, "crdt_patch is the kernels' Patch");
@@ -1683,6 +1794,8 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   for (auto& x : e->ev_blame)
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
+  for (auto& x : e->ev_enc)
+    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   *out = e.release();
   return 0;
 }
@@ -1699,6 +1812,8 @@ void crdt_engine_destroy(crdt_engine* e) {
   for (auto& x : e->ev_co)
     if (x) (void)hipEventDestroy(x);
   for (auto& x : e->ev_blame)
+    if (x) (void)hipEventDestroy(x);
+  for (auto& x : e->ev_enc)
     if (x) (void)hipEventDestroy(x);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -2424,6 +2539,7 @@ uint64_t crdt_mem_bytes(const crdt_engine* e) {
          (e->co_bm_cap + e->co_rk_cap + e->co_opos_cap + 2 * e->co_out_cap) * 4 +
          e->co_n_cap * (4 + 4 + 8 + 8 + sizeof(CoRes)) +
          e->blame_run_cap * sizeof(BlameRun) + e->blame_n_cap * (4 + sizeof(BlameRes)) +
+         e->enc_unit_cap + e->enc_sp_cap * 4 + e->enc_n_cap * (4 + 8 + sizeof(EncRes)) +
          e->n_docs * (sizeof(DocState) + sizeof(DocSeg) + 4 + 4 + 8);
 }
 
@@ -2664,6 +2780,155 @@ int crdt_last_blame_ms(crdt_engine* e, double* ms) {
     if (r) return r;
   }
   *ms = e->last_blame_ms;
+  return 0;
+}
+
+int crdt_encode_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, int enc) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n_docs && !docs) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
+  if (enc != CRDT_ENC_UTF8 && enc != CRDT_ENC_UTF16) {
+    g_last_error = "encode: enc is CRDT_ENC_UTF8 or CRDT_ENC_UTF16";
+    return CRDT_E_ARG;
+  }
+  g_alloc_oom = false;
+  int r = e->encode(n_docs, docs, (u32)enc);
+  // (no relayout is involved: an allocation that fails leaves the engine as it was, without an encode result)
+  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
+  return r;
+}
+
+// result i of the last encode, or nullptr (with the error text set) when the index has none
+static const EncRes* enc_result(crdt_engine* e, uint64_t i) {
+  if (i >= e->enc_n) return nullptr;
+  const EncRes& x = e->enc_res_h[i];
+  if (x.units == INVALID) {
+    g_last_error = "encode: a poisoned document, or one without content (or with too short a stream)";
+    return nullptr;
+  }
+  return &x;
+}
+
+int crdt_encode_lens(crdt_engine* e, uint32_t* units, uint32_t* chars) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->enc_finish();
+  if (r) return r;
+  for (u64 i = 0; i < e->enc_n; i++) {
+    if (units) units[i] = e->enc_res_h[i].units;
+    if (chars) chars[i] = e->enc_res_h[i].chars;
+  }
+  return 0;
+}
+
+int crdt_encode_read(crdt_engine* e, uint64_t i, void* out, uint64_t cap_units) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->enc_finish();
+  if (r) return r;
+  const EncRes* x = enc_result(e, i);
+  if (!x || cap_units < x->units || (x->units && !out)) return CRDT_E_ARG;
+  u64 usz = e->enc_mode == ENC_UTF8 ? 1u : 2u;
+  if (x->units) HIPCHK(hipMemcpy(out, e->enc_units + x->off * usz, (u64)x->units * usz, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int crdt_last_encode_ms(crdt_engine* e, double* ms) {
+  if (!e || !ms) return CRDT_E_ARG;
+  if (e->enc_valid && !e->enc_pulled) {
+    int r = e->enc_finish();
+    if (r) return r;
+  }
+  *ms = e->last_enc_ms;
+  return 0;
+}
+
+static int enc_query_ok(crdt_engine* e) {
+  if (!e->enc_valid) {
+    g_last_error = "encode: no encode result";
+    return CRDT_E_ARG;
+  }
+  return 0;
+}
+
+int crdt_pos_to_units_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, uint32_t* unit) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = enc_query_ok(e);
+  if (r) return r;
+  if (!n) return 0;
+  u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
+  if (e->enc_mode == ENC_UTF8)
+    hipLaunchKernelGGL(k_pos_to_units<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc_n, n, idx, pos, unit);
+  else
+    hipLaunchKernelGGL(k_pos_to_units<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc_n, n, idx, pos, unit);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int crdt_units_to_pos_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* unit, uint32_t* pos,
+                                uint8_t* mid) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = enc_query_ok(e);
+  if (r) return r;
+  if (!n) return 0;
+  u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
+  if (e->enc_mode == ENC_UTF8)
+    hipLaunchKernelGGL(k_units_to_pos<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc_n, n, idx, unit, pos, mid);
+  else
+    hipLaunchKernelGGL(k_units_to_pos<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc_n, n, idx, unit, pos, mid);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the host forms name only indexes that have a result (checked before anything is written)
+static int enc_idx_ok(crdt_engine* e, uint64_t n, const uint32_t* idx) {
+  int r = enc_query_ok(e);
+  if (r) return r;
+  r = e->enc_finish();
+  if (r) return r;
+  for (uint64_t q = 0; q < n; q++)
+    if (!enc_result(e, idx[q])) return CRDT_E_ARG;
+  return 0;
+}
+
+int crdt_pos_to_units(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, uint32_t* unit) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n && (!idx || !pos || !unit))) return CRDT_E_ARG;
+  int r = enc_idx_ok(e, n, idx);
+  if (r || !n) return r;
+  r = e->scratch(n * (4 + 4 + 4) + 64);
+  if (r) return r;
+  u32* d_idx = (u32*)e->qbuf;
+  u32* d_pos = d_idx + n;
+  u32* d_unit = d_pos + n;
+  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_pos, pos, n * 4, hipMemcpyHostToDevice, e->stream));
+  r = crdt_pos_to_units_dev_async(e, n, d_idx, d_pos, d_unit);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(unit, d_unit, n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int crdt_units_to_pos(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* unit, uint32_t* pos, uint8_t* mid) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n && (!idx || !unit || !pos))) return CRDT_E_ARG;
+  int r = enc_idx_ok(e, n, idx);
+  if (r || !n) return r;
+  r = e->scratch(n * (4 + 4 + 4 + 1) + 64);
+  if (r) return r;
+  u32* d_idx = (u32*)e->qbuf;
+  u32* d_unit = d_idx + n;
+  u32* d_pos = d_unit + n;
+  u8* d_mid = (u8*)(d_pos + n);
+  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_unit, unit, n * 4, hipMemcpyHostToDevice, e->stream));
+  r = crdt_units_to_pos_dev_async(e, n, d_idx, d_unit, d_pos, mid ? d_mid : nullptr);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(pos, d_pos, n * 4, hipMemcpyDeviceToHost, e->stream));
+  if (mid) HIPCHK(hipMemcpyAsync(mid, d_mid, n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 }
 
