@@ -338,6 +338,69 @@ int crdt_units_to_pos_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx,
                                 uint32_t* pos, uint8_t* mid);
 int crdt_last_encode_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
 
+/* ---- line index: line counts, line starts, (line, column) <-> position -------------------------
+ * An LSP Position is (line, character in UTF-16 units); a compiler diagnostic is line:column in
+ * bytes.  These calls index the lines of the last encode result on the device: index i of the line
+ * index is index i of that encode.
+ *
+ *  - The text is the encoded text of crdt_encode_async: its units and its chars.
+ *  - CRDT_EOL_LF: a break follows every U+000A.
+ *  - CRDT_EOL_ANY: a break follows every U+000A, and every U+000D that is not immediately followed
+ *    by U+000A in the same document.  CR LF is one break, after the LF; a CR that is the document's
+ *    last char is a break.
+ *  - No other char breaks a line in either mode (not U+000B, U+000C, U+0085, U+2028, U+2029).
+ *  - Line 0 starts at unit 0, char 0; line k >= 1 starts at the unit and char after the k-th break.
+ *  - n_lines = breaks + 1: an empty document has one (empty) line, and a text that ends in a break
+ *    has an empty last line.
+ *  - A line's extent runs from its start to the next line's start, its terminator included; the
+ *    last line's runs to {units, chars}.
+ *  - pos -> (line, col): for pos <= chars the line is the last one whose start char is <= pos;
+ *    col = pos - start.pos (CRDT_COL_CHARS), or (units before char pos) - start.unit
+ *    (CRDT_COL_UNITS: bytes after CRDT_ENC_UTF8, UTF-16 code units after CRDT_ENC_UTF16).
+ *    pos == chars is the end-of-document cursor on the last line; pos > chars gives line and col
+ *    0xFFFFFFFF.
+ *  - (line, col) -> pos: valid iff line < n_lines and col < the line's extent in that column kind;
+ *    on the last line col == extent is valid too and gives chars.  Otherwise pos is 0xFFFFFFFF and
+ *    mid 0.  With CRDT_COL_UNITS a column that falls inside a char gives that char with mid = 1, as
+ *    the units -> pos mapping of the encode does.  The two mappings are inverse bijections between
+ *    [0, chars] and the valid (line, col) pairs with mid == 0.  (A caller that wants the LSP clamp
+ *    reads the extents from the line starts.) */
+enum { CRDT_EOL_LF = 0, CRDT_EOL_ANY = 1 };
+enum { CRDT_COL_UNITS = 0, CRDT_COL_CHARS = 1 };
+typedef struct { uint32_t unit, pos; } crdt_line_start;
+/* Index, on the device and stream-ordered, the lines of every index of the last encode (the call
+ * waits once inside, for the total that sizes the table).  CRDT_E_ARG before any encode result and
+ * for an unknown eol.  Replaces the previous line index: a second call on the same encode is how a
+ * caller switches eol.  Changes no document, and neither the encode result nor the diff result, the
+ * checkout and the blame result.  The line index belongs to the encode result it was built from:
+ * a later encode call, successful or not, drops it, and so does crdt_docs_alloc; the reads and
+ * queries below then return CRDT_E_ARG until the next line index is built.  Until then it stays
+ * valid whatever is replayed, published or materialised: the kernels read nothing but the encode
+ * result and the line table.
+ * CRDT_E_NOMEM if an allocation fails: the engine stays usable, without a line index and with the
+ * encode result intact. */
+int crdt_lines_async(crdt_engine* e, int eol);
+/* Lines per index of that encode (syncs).  An index the encode has no result for has none here:
+ * its count is 0xFFFFFFFF, reading its starts returns CRDT_E_ARG, and a host-form query that names
+ * it returns CRDT_E_ARG for the whole call and writes nothing (as does an idx out of range). */
+int crdt_line_counts(crdt_engine* e, uint32_t* n_lines);
+/* The starts of the n_lines[i] lines of index i; the first is {0, 0}. */
+int crdt_lines_read(crdt_engine* e, uint64_t i, crdt_line_start* starts);
+/* The two mappings (above); idx[q] names an index of the encode.  An unknown col_kind is
+ * CRDT_E_ARG; mid may be NULL. */
+int crdt_pos_to_linecol(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, int col_kind,
+                        uint32_t* line, uint32_t* col);
+int crdt_linecol_to_pos(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* line, const uint32_t* col,
+                        int col_kind, uint32_t* pos, uint8_t* mid);
+/* Device-pointer forms (inputs/outputs already in HBM; async on the engine stream).  idx cannot be
+ * checked on the host: a query whose idx is out of range or has no result is answered 0xFFFFFFFF
+ * (line and col, or pos with mid = 0). */
+int crdt_pos_to_linecol_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, int col_kind,
+                                  uint32_t* line, uint32_t* col);
+int crdt_linecol_to_pos_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* line,
+                                  const uint32_t* col, int col_kind, uint32_t* pos, uint8_t* mid);
+int crdt_last_lines_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
+
 /* ListCRDT::len (doc.rs:484-486) */
 int crdt_doc_len(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* len);
 int crdt_doc_status(crdt_engine* e, int32_t* status /* n_docs */);

@@ -305,6 +305,14 @@ def lib():
     L.crdt_pos_to_units_dev_async.argtypes = [vp, u64, vp, vp, vp]
     L.crdt_units_to_pos_dev_async.argtypes = [vp, u64, vp, vp, vp, vp]
     L.crdt_last_encode_ms.argtypes = [vp, P(C.c_double)]
+    L.crdt_lines_async.argtypes = [vp, C.c_int]
+    L.crdt_line_counts.argtypes = [vp, P(u32)]
+    L.crdt_lines_read.argtypes = [vp, u64, vp]
+    L.crdt_pos_to_linecol.argtypes = [vp, u64, P(u32), P(u32), C.c_int, P(u32), P(u32)]
+    L.crdt_linecol_to_pos.argtypes = [vp, u64, P(u32), P(u32), P(u32), C.c_int, P(u32), P(C.c_uint8)]
+    L.crdt_pos_to_linecol_dev_async.argtypes = [vp, u64, vp, vp, C.c_int, vp, vp]
+    L.crdt_linecol_to_pos_dev_async.argtypes = [vp, u64, vp, vp, vp, C.c_int, vp, vp]
+    L.crdt_last_lines_ms.argtypes = [vp, P(C.c_double)]
     L.crdt_last_error.restype = C.c_char_p
     L.crdt_trace_load.argtypes = [C.c_char_p, P(vp)]
     L.crdt_trace_parse.argtypes = [C.c_char_p, u64, P(vp)]
@@ -332,6 +340,8 @@ EXPORTED_SYMBOLS = [
     "crdt_blame_async", "crdt_blame_counts", "crdt_blame_read", "crdt_last_blame_ms",
     "crdt_encode_async", "crdt_encode_lens", "crdt_encode_read", "crdt_pos_to_units", "crdt_units_to_pos",
     "crdt_pos_to_units_dev_async", "crdt_units_to_pos_dev_async", "crdt_last_encode_ms",
+    "crdt_lines_async", "crdt_line_counts", "crdt_lines_read", "crdt_pos_to_linecol", "crdt_linecol_to_pos",
+    "crdt_pos_to_linecol_dev_async", "crdt_linecol_to_pos_dev_async", "crdt_last_lines_ms",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -913,6 +923,72 @@ class Engine:
         _check(self.L.crdt_last_encode_ms(self.h, C.byref(x)), "last_encode_ms")
         return x.value
 
+    # --- line index of the last encode (crdt_gpu.h "line index")
+    EOLS = {"lf": 0, "any": 1}
+    COL_KINDS = {"units": 0, "chars": 1}
+
+    def lines_async(self, eol):
+        """index the lines of every index of the last encode on the device; eol is "lf" / "any" (or
+        CRDT_EOL_LF = 0 / CRDT_EOL_ANY = 1); replaces the last line index"""
+        _check(self.L.crdt_lines_async(self.h, int(self.EOLS.get(eol, eol))), "lines_async")
+
+    def line_counts(self) -> np.ndarray:
+        """lines per index of the last encode; 0xFFFFFFFF marks an index without a result"""
+        out = np.zeros(getattr(self, "_enc_n", 0), np.uint32)
+        _check(self.L.crdt_line_counts(self.h, _p(out)), "line_counts")
+        return out
+
+    def lines_read(self, i: int, counts=None) -> np.ndarray:
+        """the line starts of index i: [n_lines, 2] u32 = (unit, pos); raises CrdtError (rc=-100) for
+        an index without a result"""
+        counts = counts if counts is not None else self.line_counts()
+        bad = not 0 <= i < len(counts) or int(counts[i]) == 0xFFFFFFFF  # (the library answers CRDT_E_ARG)
+        out = np.zeros((1 if bad else int(counts[i]), 2), np.uint32)
+        _check(self.L.crdt_lines_read(self.h, i, out.ctypes.data), "lines_read")
+        return out
+
+    def lines(self, eol="lf", strict: bool = True):
+        """[line starts (n_lines, 2) u32 = (unit, pos)] per index of the last encode.  An index
+        without a result raises CrdtError, or is None with strict=False."""
+        self.lines_async(eol)
+        counts = self.line_counts()
+        bad = np.flatnonzero(counts == 0xFFFFFFFF)
+        if strict and bad.size:
+            raise CrdtError(f"lines failed rc=-100 for indexes {bad.tolist()}: the encode has no result for them")
+        return [None if int(counts[i]) == 0xFFFFFFFF else self.lines_read(i, counts) for i in range(len(counts))]
+
+    def pos_to_linecol(self, idx, pos, col="units"):
+        """(line, col) of char pos[q] of index idx[q]; col counts "units" of the encode or "chars"
+        (0xFFFFFFFF for both: pos above its chars)"""
+        i = np.ascontiguousarray(idx, dtype=np.uint32)
+        p = np.ascontiguousarray(pos, dtype=np.uint32)
+        if i.shape != p.shape or i.ndim != 1:
+            raise ValueError("pos_to_linecol: idx and pos are 1-d and of equal length")
+        ln, c = np.zeros(p.shape[0], np.uint32), np.zeros(p.shape[0], np.uint32)
+        _check(self.L.crdt_pos_to_linecol(self.h, p.shape[0], _p(i), _p(p), int(self.COL_KINDS.get(col, col)), _p(ln), _p(c)),
+               "pos_to_linecol")
+        return ln, c
+
+    def linecol_to_pos(self, idx, line, col, kind="units"):
+        """(pos, mid): the char at column col[q] ("units" of the encode, or "chars") of line line[q] of
+        index idx[q], and whether a unit column falls inside it (0xFFFFFFFF, 0: no such line or column)"""
+        i = np.ascontiguousarray(idx, dtype=np.uint32)
+        ln = np.ascontiguousarray(line, dtype=np.uint32)
+        c = np.ascontiguousarray(col, dtype=np.uint32)
+        if not i.shape == ln.shape == c.shape or i.ndim != 1:
+            raise ValueError("linecol_to_pos: idx, line and col are 1-d and of equal length")
+        p = np.zeros(c.shape[0], np.uint32)
+        m = np.zeros(c.shape[0], np.uint8)
+        _check(self.L.crdt_linecol_to_pos(self.h, c.shape[0], _p(i), _p(ln), _p(c), int(self.COL_KINDS.get(kind, kind)), _p(p),
+                                          _p(m, C.c_uint8)), "linecol_to_pos")
+        return p, m
+
+    def lines_ms(self) -> float:
+        """device time of the last line index (HIP events)"""
+        x = C.c_double()
+        _check(self.L.crdt_last_lines_ms(self.h, C.byref(x)), "last_lines_ms")
+        return x.value
+
     def timings(self):
         a, b = C.c_double(), C.c_double()
         self.L.crdt_last_timings(self.h, C.byref(a), C.byref(b))
@@ -987,6 +1063,24 @@ class ListCRDT:
         if n == 0xFFFFFFFF:
             raise CrdtError("len_utf16 failed rc=-100: a poisoned document, or one without content")
         return n
+
+    def line_count(self, eol: str = "lf") -> int:
+        """lines of the text (breaks + 1); eol "lf", or "any" for LF, CR LF and lone CR"""
+        self.e.encode([0], "utf8")
+        return int(self.e.lines(eol)[0].shape[0])
+
+    def pos_to_linecol(self, pos: int, enc: str = "utf16", eol: str = "lf", col: str = "units"):
+        """(line, col) of char `pos`; col in units of `enc` (an LSP Position with "utf16"), or in "chars" """
+        self.e.encode([0], enc)
+        self.e.lines_async(eol)
+        ln, c = self.e.pos_to_linecol([0], [pos], col)
+        return int(ln[0]), int(c[0])
+
+    def linecol_to_pos(self, line: int, col: int, enc: str = "utf16", eol: str = "lf", kind: str = "units") -> int:
+        """the char position of (line, col); 0xFFFFFFFF if there is no such line or column"""
+        self.e.encode([0], enc)
+        self.e.lines_async(eol)
+        return int(self.e.linecol_to_pos([0], [line], [col], kind)[0][0])
 
     def status(self) -> int:
         return int(self.e.status()[0])

@@ -17,6 +17,7 @@
 #include "host_plan.h"
 #include "kernels.h"
 #include "encode.h"
+#include "lines.h"
 
 using namespace crdt;
 
@@ -340,6 +341,18 @@ struct crdt_engine {
   bool enc_valid = false;   // an encode result exists (crdt_encode_async succeeded since the last crdt_docs_alloc)
   bool enc_pulled = false;  // ... and enc_res_h / last_enc_ms hold it
   double last_enc_ms = 0;
+  // line index (crdt_lines_async): belongs to the encode result it was built from (crdt_encode_async
+  // drops it: ln_valid implies enc_valid); buffers of its own, kept and grown from call to call like
+  // the encode's
+  hipEvent_t ev_ln[2] = {nullptr, nullptr};
+  std::vector<LnRes> ln_res_h;
+  LnRes* ln_res = nullptr;
+  u64* ln_tot = nullptr;
+  LineStart* ln_tab = nullptr;
+  u64 ln_n_cap = 0, ln_tab_cap = 0;
+  bool ln_valid = false;   // a line index of the current encode result exists
+  bool ln_pulled = false;  // ... and ln_res_h / last_ln_ms hold it
+  double last_ln_ms = 0;
 
   Pools pools_view(const PoolSet& ps) const {
     Pools p{};
@@ -421,6 +434,9 @@ struct crdt_engine {
     enc_n_cap = enc_sp_cap = enc_unit_cap = 0;
     enc_n = 0;
     enc_valid = enc_pulled = false;
+    dfree(ln_res); dfree(ln_tot); dfree(ln_tab);
+    ln_n_cap = ln_tab_cap = 0;
+    ln_valid = ln_pulled = false;
   }
 
   int set_device() {
@@ -1730,7 +1746,82 @@ struct crdt_engine {
     enc_pulled = true;
     return 0;
   }
+
+  LnIO ln_view() const {
+    LnIO io{};
+    io.res = ln_res;
+    io.tab = ln_tab;
+    return io;
+  }
+  // crdt_lines_async: count every index's breaks over its units of the pool, scan the counts into
+  // table offsets on the device, size the table from the total (the one host read between the
+  // sweeps: 8 bytes), write the line starts.
+  int lines(u32 eol) {
+    int r = set_device();
+    if (r) return r;
+    ln_valid = ln_pulled = false;
+    u64 n = enc_n;
+    if (!n) {
+      ln_valid = true;
+      return 0;
+    }
+    if (n > ln_n_cap) {
+      HIPCHK(hipStreamSynchronize(stream));
+      dfree(ln_res);
+      ln_n_cap = 0;
+      HIPCHK(dalloc(ln_res, n));
+      ln_n_cap = n;
+    }
+    if (!ln_tot) HIPCHK(dalloc(ln_tot, 1));
+    HIPCHK(hipEventRecord(ev_ln[0], stream));
+    EncIO ev = enc_view();
+    u32 inst = enc_mode * 2u + eol;
+    switch (inst) {
+      case 0: hipLaunchKernelGGL((k_ln_count<ENC_UTF8, EOL_LF>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
+      case 1: hipLaunchKernelGGL((k_ln_count<ENC_UTF8, EOL_ANY>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
+      case 2: hipLaunchKernelGGL((k_ln_count<ENC_UTF16, EOL_LF>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
+      default: hipLaunchKernelGGL((k_ln_count<ENC_UTF16, EOL_ANY>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
+    }
+    hipLaunchKernelGGL(k_ln_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, ln_res, (u32)n, ln_tot);
+    HIPCHK(hipGetLastError());
+    u64 tot = 0;
+    HIPCHK(hipMemcpyAsync(&tot, ln_tot, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    r = diff_grow(ln_tab, ln_tab_cap, tot);
+    if (r) return r;
+    switch (inst) {
+      case 0: hipLaunchKernelGGL((k_ln_write<ENC_UTF8, EOL_LF>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
+      case 1: hipLaunchKernelGGL((k_ln_write<ENC_UTF8, EOL_ANY>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
+      case 2: hipLaunchKernelGGL((k_ln_write<ENC_UTF16, EOL_LF>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
+      default: hipLaunchKernelGGL((k_ln_write<ENC_UTF16, EOL_ANY>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev_ln[1], stream));
+    ln_valid = true;
+    return 0;
+  }
+  // the per-index line counts and the device time of the last line index, on the host (waits for it)
+  int ln_finish() {
+    if (!ln_valid) return CRDT_E_ARG;
+    if (ln_pulled) return 0;
+    int r = set_device();
+    if (r) return r;
+    ln_res_h.resize(enc_n);
+    last_ln_ms = 0;
+    if (enc_n) {
+      HIPCHK(hipMemcpyAsync(ln_res_h.data(), ln_res, enc_n * sizeof(LnRes), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, ev_ln[0], ev_ln[1]);
+      last_ln_ms = ms;
+    }
+    ln_pulled = true;
+    return 0;
+  }
 };
+static_assert(EOL_LF == CRDT_EOL_LF && EOL_ANY == CRDT_EOL_ANY, "CRDT_EOL_* are the kernels' modes");
+static_assert(COL_UNITS == CRDT_COL_UNITS && COL_CHARS == CRDT_COL_CHARS, "CRDT_COL_* are the kernels' column kinds");
+static_assert(sizeof(LineStart) == sizeof(crdt_line_start) && sizeof(crdt_line_start) == 8, "crdt_line_start is the kernels' LineStart");
 static_assert(ENC_UTF8 == CRDT_ENC_UTF8 && ENC_UTF16 == CRDT_ENC_UTF16, "CRDT_ENC_* are the kernels' encodings");
 static_assert(sizeof(BlameRun) == sizeof(crdt_blame_run) && sizeof(crdt_blame_run) == 16, "crdt_blame_run is the kernels' BlameRun");
 static_assert(BLAME_AGENT == CRDT_BLAME_AGENT && BLAME_ID == CRDT_BLAME_ID, "CRDT_BLAME_* are the kernels' modes");
@@ -1796,6 +1887,8 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   for (auto& x : e->ev_enc)
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
+  for (auto& x : e->ev_ln)
+    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   *out = e.release();
   return 0;
 }
@@ -1814,6 +1907,8 @@ void crdt_engine_destroy(crdt_engine* e) {
   for (auto& x : e->ev_blame)
     if (x) (void)hipEventDestroy(x);
   for (auto& x : e->ev_enc)
+    if (x) (void)hipEventDestroy(x);
+  for (auto& x : e->ev_ln)
     if (x) (void)hipEventDestroy(x);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -2540,6 +2635,7 @@ uint64_t crdt_mem_bytes(const crdt_engine* e) {
          e->co_n_cap * (4 + 4 + 8 + 8 + sizeof(CoRes)) +
          e->blame_run_cap * sizeof(BlameRun) + e->blame_n_cap * (4 + sizeof(BlameRes)) +
          e->enc_unit_cap + e->enc_sp_cap * 4 + e->enc_n_cap * (4 + 8 + sizeof(EncRes)) +
+         e->ln_tab_cap * sizeof(LineStart) + e->ln_n_cap * sizeof(LnRes) +
          e->n_docs * (sizeof(DocState) + sizeof(DocSeg) + 4 + 4 + 8);
 }
 
@@ -2785,6 +2881,7 @@ int crdt_last_blame_ms(crdt_engine* e, double* ms) {
 
 int crdt_encode_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, int enc) {
   if (poisoned(e)) return CRDT_E_NOMEM;
+  if (e) e->ln_valid = e->ln_pulled = false;  // (a later encode call, successful or not, drops the line index)
   if (!valid(e) || (n_docs && !docs) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
   if (enc != CRDT_ENC_UTF8 && enc != CRDT_ENC_UTF16) {
     g_last_error = "encode: enc is CRDT_ENC_UTF8 or CRDT_ENC_UTF16";
@@ -2925,6 +3022,181 @@ int crdt_units_to_pos(crdt_engine* e, uint64_t n, const uint32_t* idx, const uin
   HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipMemcpyAsync(d_unit, unit, n * 4, hipMemcpyHostToDevice, e->stream));
   r = crdt_units_to_pos_dev_async(e, n, d_idx, d_unit, d_pos, mid ? d_mid : nullptr);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(pos, d_pos, n * 4, hipMemcpyDeviceToHost, e->stream));
+  if (mid) HIPCHK(hipMemcpyAsync(mid, d_mid, n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int crdt_lines_async(crdt_engine* e, int eol) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  if (eol != CRDT_EOL_LF && eol != CRDT_EOL_ANY) {
+    g_last_error = "lines: eol is CRDT_EOL_LF or CRDT_EOL_ANY";
+    return CRDT_E_ARG;
+  }
+  int r = enc_query_ok(e);
+  if (r) return r;
+  g_alloc_oom = false;
+  r = e->lines((u32)eol);
+  // (an allocation that fails leaves the engine as it was, with its encode result and without a line index)
+  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
+  return r;
+}
+
+static int ln_query_ok(crdt_engine* e) {
+  if (!e->ln_valid) {
+    g_last_error = "lines: no line index (of the current encode result)";
+    return CRDT_E_ARG;
+  }
+  return 0;
+}
+static int col_kind_ok(int col_kind) {
+  if (col_kind != CRDT_COL_UNITS && col_kind != CRDT_COL_CHARS) {
+    g_last_error = "lines: col_kind is CRDT_COL_UNITS or CRDT_COL_CHARS";
+    return CRDT_E_ARG;
+  }
+  return 0;
+}
+// line count i of the last line index, or nullptr (with the error text set) when the index has none
+static const LnRes* ln_result(crdt_engine* e, uint64_t i) {
+  if (i >= e->enc_n) return nullptr;
+  const LnRes& x = e->ln_res_h[i];
+  if (x.n_lines == INVALID) {
+    g_last_error = "lines: the encode has no result for this index";
+    return nullptr;
+  }
+  return &x;
+}
+
+int crdt_line_counts(crdt_engine* e, uint32_t* n_lines) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = ln_query_ok(e);
+  if (r) return r;
+  r = e->ln_finish();
+  if (r) return r;
+  for (u64 i = 0; i < e->enc_n; i++)
+    if (n_lines) n_lines[i] = e->ln_res_h[i].n_lines;
+  return 0;
+}
+
+int crdt_lines_read(crdt_engine* e, uint64_t i, crdt_line_start* starts) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = ln_query_ok(e);
+  if (r) return r;
+  r = e->ln_finish();
+  if (r) return r;
+  const LnRes* x = ln_result(e, i);
+  if (!x || !starts) return CRDT_E_ARG;
+  HIPCHK(hipMemcpy(starts, e->ln_tab + x->off, (u64)x->n_lines * sizeof(LineStart), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int crdt_last_lines_ms(crdt_engine* e, double* ms) {
+  if (!e || !ms) return CRDT_E_ARG;
+  if (e->ln_valid && !e->ln_pulled) {
+    int r = e->ln_finish();
+    if (r) return r;
+  }
+  *ms = e->last_ln_ms;
+  return 0;
+}
+
+int crdt_pos_to_linecol_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, int col_kind,
+                                  uint32_t* line, uint32_t* col) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = col_kind_ok(col_kind);
+  if (r) return r;
+  r = ln_query_ok(e);
+  if (r) return r;
+  if (!n) return 0;
+  u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
+  if (e->enc_mode == ENC_UTF8)
+    hipLaunchKernelGGL(k_pos_to_linecol<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc_n, n,
+                       idx, pos, (u32)col_kind, line, col);
+  else
+    hipLaunchKernelGGL(k_pos_to_linecol<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc_n, n,
+                       idx, pos, (u32)col_kind, line, col);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int crdt_linecol_to_pos_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* line, const uint32_t* col,
+                                  int col_kind, uint32_t* pos, uint8_t* mid) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = col_kind_ok(col_kind);
+  if (r) return r;
+  r = ln_query_ok(e);
+  if (r) return r;
+  if (!n) return 0;
+  u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
+  if (e->enc_mode == ENC_UTF8)
+    hipLaunchKernelGGL(k_linecol_to_pos<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc_n, n,
+                       idx, line, col, (u32)col_kind, pos, mid);
+  else
+    hipLaunchKernelGGL(k_linecol_to_pos<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc_n, n,
+                       idx, line, col, (u32)col_kind, pos, mid);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the host forms name only indexes that have a result (checked before anything is written)
+static int ln_idx_ok(crdt_engine* e, uint64_t n, const uint32_t* idx, int col_kind) {
+  int r = col_kind_ok(col_kind);
+  if (r) return r;
+  r = ln_query_ok(e);
+  if (r) return r;
+  r = e->ln_finish();
+  if (r) return r;
+  for (uint64_t q = 0; q < n; q++)
+    if (!ln_result(e, idx[q])) return CRDT_E_ARG;
+  return 0;
+}
+
+int crdt_pos_to_linecol(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, int col_kind, uint32_t* line,
+                        uint32_t* col) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n && (!idx || !pos || !line || !col))) return CRDT_E_ARG;
+  int r = ln_idx_ok(e, n, idx, col_kind);
+  if (r || !n) return r;
+  r = e->scratch(n * (4 + 4 + 4 + 4) + 64);
+  if (r) return r;
+  u32* d_idx = (u32*)e->qbuf;
+  u32* d_pos = d_idx + n;
+  u32* d_line = d_pos + n;
+  u32* d_col = d_line + n;
+  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_pos, pos, n * 4, hipMemcpyHostToDevice, e->stream));
+  r = crdt_pos_to_linecol_dev_async(e, n, d_idx, d_pos, col_kind, d_line, d_col);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(line, d_line, n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(col, d_col, n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int crdt_linecol_to_pos(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* line, const uint32_t* col,
+                        int col_kind, uint32_t* pos, uint8_t* mid) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n && (!idx || !line || !col || !pos))) return CRDT_E_ARG;
+  int r = ln_idx_ok(e, n, idx, col_kind);
+  if (r || !n) return r;
+  r = e->scratch(n * (4 + 4 + 4 + 4 + 1) + 64);
+  if (r) return r;
+  u32* d_idx = (u32*)e->qbuf;
+  u32* d_line = d_idx + n;
+  u32* d_col = d_line + n;
+  u32* d_pos = d_col + n;
+  u8* d_mid = (u8*)(d_pos + n);
+  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_line, line, n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_col, col, n * 4, hipMemcpyHostToDevice, e->stream));
+  r = crdt_linecol_to_pos_dev_async(e, n, d_idx, d_line, d_col, col_kind, d_pos, mid ? d_mid : nullptr);
   if (r) return r;
   HIPCHK(hipMemcpyAsync(pos, d_pos, n * 4, hipMemcpyDeviceToHost, e->stream));
   if (mid) HIPCHK(hipMemcpyAsync(mid, d_mid, n, hipMemcpyDeviceToHost, e->stream));
