@@ -401,6 +401,60 @@ int crdt_linecol_to_pos_dev_async(crdt_engine* e, uint64_t n, const uint32_t* id
                                   const uint32_t* col, int col_kind, uint32_t* pos, uint8_t* mid);
 int crdt_last_lines_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
 
+/* ---- find: every occurrence of a literal pattern in the encoded text -----------------------------
+ * Searches every index of the last encode result on the device with one pattern: index i of the
+ * find result is index i of that encode.
+ *
+ *  - The text of index i is the text of the last encode: chars items T[0..chars).  Each content
+ *    value is sanitised as the encoder sanitises it (a surrogate or a value above 0x10FFFF is
+ *    U+FFFD).
+ *  - The pattern is given as UTF-32 code points P[0..m), like content, 1 <= m <=
+ *    CRDT_FIND_MAX_CHARS, and is sanitised the same way: a pattern value that is no scalar value
+ *    matches U+FFFD, and content that was no scalar value is matched by a pattern char U+FFFD.
+ *  - fold(c) = c + 0x20 for 0x41 <= c <= 0x5A with CRDT_FIND_ASCII_ICASE, else c.  Nothing outside
+ *    ASCII folds (not U+212A, not U+0130, not U+00C9).
+ *  - A match at char position p exists iff p + m <= chars and fold(T[p + j]) == fold(P[j]) for all
+ *    j < m.  All matches are reported, overlapping ones included ("aa" in "aaaa": 0, 1, 2).  A
+ *    match lies wholly inside one document.  An empty document, or one shorter than the pattern,
+ *    has 0 matches: that is a result.
+ *  - Each match is {unit, pos}: pos = p, unit = the units before char p in that encode (what
+ *    crdt_pos_to_units answers for p).  Matches come in ascending order.
+ *  - (line, column) of a match: crdt_pos_to_linecol of its pos.  Non-overlapping "replace all"
+ *    semantics: filter the sorted list greedily on the host. */
+enum { CRDT_FIND_EXACT = 0, CRDT_FIND_ASCII_ICASE = 1 };
+#define CRDT_FIND_MAX_CHARS 64
+typedef struct { uint32_t unit, pos; } crdt_match;
+/* Search, on the device and stream-ordered, every index of the last encode (the call waits once
+ * inside, for the total that sizes the match table).  CRDT_E_ARG before any encode result, for
+ * n_chars == 0 or above CRDT_FIND_MAX_CHARS, for a NULL pattern and for an unknown flag bit.
+ * Replaces the previous find result.  Changes no document, and neither the encode result nor the
+ * line index, the diff result, the checkout and the blame result; crdt_lines_async does not touch
+ * the find result either.  The find result belongs to the encode result it was built from: a later
+ * encode call, successful or not, drops it, and so does crdt_docs_alloc; the reads and seeks below
+ * then return CRDT_E_ARG until the next find.  Until then it stays valid whatever is replayed,
+ * published or materialised: the seeks read nothing but the match table.
+ * CRDT_E_NOMEM if an allocation fails: the engine stays usable, without a find result and with the
+ * encode result and the line index intact. */
+int crdt_find_async(crdt_engine* e, const uint32_t* pattern, uint32_t n_chars, int flags);
+/* Matches per index of that encode (syncs).  An index the encode has no result for has none here:
+ * its count is 0xFFFFFFFF, reading its matches returns CRDT_E_ARG, and a host-form seek that names
+ * it returns CRDT_E_ARG for the whole call and writes nothing (as does an idx out of range). */
+int crdt_find_counts(crdt_engine* e, uint32_t* n_matches);
+/* The n_matches[i] matches of index i (matches may be NULL when there are none). */
+int crdt_find_read(crdt_engine* e, uint64_t i, crdt_match* matches);
+/* Find next / previous from the cursor: k[q] is the number, within index idx[q], of the first match
+ * with match.pos >= pos[q] (CRDT_SEEK_NEXT) or of the last match with match.pos <= pos[q]
+ * (CRDT_SEEK_PREV); 0xFFFFFFFF when there is none.  pos is not checked against the document's
+ * chars: the answer is a function of the match table alone, and wrapping round is the caller's
+ * business.  An unknown dir is CRDT_E_ARG. */
+enum { CRDT_SEEK_NEXT = 0, CRDT_SEEK_PREV = 1 };
+int crdt_find_seek(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, int dir, uint32_t* k);
+/* Device-pointer form (inputs/outputs already in HBM; async on the engine stream).  idx cannot be
+ * checked on the host: a query whose idx is out of range or has no result is answered 0xFFFFFFFF. */
+int crdt_find_seek_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, int dir,
+                             uint32_t* k);
+int crdt_last_find_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
+
 /* ListCRDT::len (doc.rs:484-486) */
 int crdt_doc_len(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* len);
 int crdt_doc_status(crdt_engine* e, int32_t* status /* n_docs */);

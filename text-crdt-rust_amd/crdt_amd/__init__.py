@@ -313,6 +313,12 @@ def lib():
     L.crdt_pos_to_linecol_dev_async.argtypes = [vp, u64, vp, vp, C.c_int, vp, vp]
     L.crdt_linecol_to_pos_dev_async.argtypes = [vp, u64, vp, vp, vp, C.c_int, vp, vp]
     L.crdt_last_lines_ms.argtypes = [vp, P(C.c_double)]
+    L.crdt_find_async.argtypes = [vp, P(u32), u32, C.c_int]
+    L.crdt_find_counts.argtypes = [vp, P(u32)]
+    L.crdt_find_read.argtypes = [vp, u64, vp]
+    L.crdt_find_seek.argtypes = [vp, u64, P(u32), P(u32), C.c_int, P(u32)]
+    L.crdt_find_seek_dev_async.argtypes = [vp, u64, vp, vp, C.c_int, vp]
+    L.crdt_last_find_ms.argtypes = [vp, P(C.c_double)]
     L.crdt_last_error.restype = C.c_char_p
     L.crdt_trace_load.argtypes = [C.c_char_p, P(vp)]
     L.crdt_trace_parse.argtypes = [C.c_char_p, u64, P(vp)]
@@ -342,6 +348,7 @@ EXPORTED_SYMBOLS = [
     "crdt_pos_to_units_dev_async", "crdt_units_to_pos_dev_async", "crdt_last_encode_ms",
     "crdt_lines_async", "crdt_line_counts", "crdt_lines_read", "crdt_pos_to_linecol", "crdt_linecol_to_pos",
     "crdt_pos_to_linecol_dev_async", "crdt_linecol_to_pos_dev_async", "crdt_last_lines_ms",
+    "crdt_find_async", "crdt_find_counts", "crdt_find_read", "crdt_find_seek", "crdt_find_seek_dev_async", "crdt_last_find_ms",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -989,6 +996,62 @@ class Engine:
         _check(self.L.crdt_last_lines_ms(self.h, C.byref(x)), "last_lines_ms")
         return x.value
 
+    # --- find in the last encode (crdt_gpu.h "find")
+    SEEK_DIRS = {"next": 0, "prev": 1}
+
+    def find_async(self, pattern, icase: bool = False):
+        """search every index of the last encode on the device for `pattern`: a str (its code points
+        by ord, so lone surrogates are possible) or a uint32 array of 1..64 code points; icase folds
+        ASCII A-Z only; replaces the last find result"""
+        if isinstance(pattern, str):
+            pattern = [ord(c) for c in pattern]
+        p = np.ascontiguousarray(pattern, dtype=np.uint32)
+        if p.ndim != 1:
+            raise ValueError("find: pattern is a str or 1-d")
+        _check(self.L.crdt_find_async(self.h, _p(p), p.shape[0], 1 if icase else 0), "find_async")
+
+    def find_counts(self) -> np.ndarray:
+        """matches per index of the last encode; 0xFFFFFFFF marks an index without a result"""
+        out = np.zeros(getattr(self, "_enc_n", 0), np.uint32)
+        _check(self.L.crdt_find_counts(self.h, _p(out)), "find_counts")
+        return out
+
+    def find_read(self, i: int, counts=None) -> np.ndarray:
+        """the matches of index i: [n_matches, 2] u32 = (unit, pos), ascending; raises CrdtError
+        (rc=-100) for an index without a result"""
+        counts = counts if counts is not None else self.find_counts()
+        bad = not 0 <= i < len(counts) or int(counts[i]) == 0xFFFFFFFF  # (the library answers CRDT_E_ARG)
+        out = np.zeros((0 if bad else int(counts[i]), 2), np.uint32)
+        _check(self.L.crdt_find_read(self.h, i, out.ctypes.data if out.size else None), "find_read")
+        return out
+
+    def find(self, pattern, icase: bool = False, strict: bool = True):
+        """[matches (n_matches, 2) u32 = (unit, pos)] per index of the last encode.  An index without
+        a result raises CrdtError, or is None with strict=False."""
+        self.find_async(pattern, icase)
+        counts = self.find_counts()
+        bad = np.flatnonzero(counts == 0xFFFFFFFF)
+        if strict and bad.size:
+            raise CrdtError(f"find failed rc=-100 for indexes {bad.tolist()}: the encode has no result for them")
+        return [None if int(counts[i]) == 0xFFFFFFFF else self.find_read(i, counts) for i in range(len(counts))]
+
+    def find_seek(self, idx, pos, dir="next") -> np.ndarray:
+        """the number, within index idx[q], of the first match at or after char pos[q] (dir "next") or
+        of the last match at or before it ("prev"); 0xFFFFFFFF: none"""
+        i = np.ascontiguousarray(idx, dtype=np.uint32)
+        p = np.ascontiguousarray(pos, dtype=np.uint32)
+        if i.shape != p.shape or i.ndim != 1:
+            raise ValueError("find_seek: idx and pos are 1-d and of equal length")
+        k = np.zeros(p.shape[0], np.uint32)
+        _check(self.L.crdt_find_seek(self.h, p.shape[0], _p(i), _p(p), int(self.SEEK_DIRS.get(dir, dir)), _p(k)), "find_seek")
+        return k
+
+    def find_ms(self) -> float:
+        """device time of the last find (HIP events)"""
+        x = C.c_double()
+        _check(self.L.crdt_last_find_ms(self.h, C.byref(x)), "last_find_ms")
+        return x.value
+
     def timings(self):
         a, b = C.c_double(), C.c_double()
         self.L.crdt_last_timings(self.h, C.byref(a), C.byref(b))
@@ -1081,6 +1144,12 @@ class ListCRDT:
         self.e.encode([0], enc)
         self.e.lines_async(eol)
         return int(self.e.linecol_to_pos([0], [line], [col], kind)[0][0])
+
+    def find(self, pattern, enc: str = "utf16", icase: bool = False) -> np.ndarray:
+        """every occurrence of `pattern` (a str or uint32 code points) in the text, overlapping ones
+        included: [n, 2] u32 = (unit offset in `enc`, char position), ascending"""
+        self.e.encode([0], enc)
+        return self.e.find(pattern, icase)[0]
 
     def status(self) -> int:
         return int(self.e.status()[0])

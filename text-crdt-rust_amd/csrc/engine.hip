@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "encode.h"
 #include "lines.h"
+#include "find.h"
 
 using namespace crdt;
 
@@ -353,6 +354,20 @@ struct crdt_engine {
   bool ln_valid = false;   // a line index of the current encode result exists
   bool ln_pulled = false;  // ... and ln_res_h / last_ln_ms hold it
   double last_ln_ms = 0;
+  // find result (crdt_find_async): belongs to the encode result it was built from, like the line
+  // index (crdt_encode_async drops it: fd_valid implies enc_valid); buffers of its own, kept and
+  // grown from call to call like the line index's
+  hipEvent_t ev_fd[2] = {nullptr, nullptr};
+  std::vector<FdRes> fd_res_h;
+  u32 fd_pat_h[FD_PAT_W] = {};
+  u32* fd_pat = nullptr;  // FD_PAT_W dwords: the pattern's units
+  FdRes* fd_res = nullptr;
+  u64* fd_tot = nullptr;
+  Match* fd_tab = nullptr;
+  u64 fd_n_cap = 0, fd_tab_cap = 0;
+  bool fd_valid = false;   // a find result of the current encode result exists
+  bool fd_pulled = false;  // ... and fd_res_h / last_fd_ms hold it
+  double last_fd_ms = 0;
 
   Pools pools_view(const PoolSet& ps) const {
     Pools p{};
@@ -437,6 +452,9 @@ struct crdt_engine {
     dfree(ln_res); dfree(ln_tot); dfree(ln_tab);
     ln_n_cap = ln_tab_cap = 0;
     ln_valid = ln_pulled = false;
+    dfree(fd_pat); dfree(fd_res); dfree(fd_tot); dfree(fd_tab);
+    fd_n_cap = fd_tab_cap = 0;
+    fd_valid = fd_pulled = false;
   }
 
   int set_device() {
@@ -1818,7 +1836,113 @@ struct crdt_engine {
     ln_pulled = true;
     return 0;
   }
+
+  FdIO fd_view() const {
+    FdIO io{};
+    io.res = fd_res;
+    io.tab = fd_tab;
+    return io;
+  }
+  // crdt_find_async: sanitise, fold and encode the pattern into the encode's units, count every
+  // index's matches over its units of the pool, scan the counts into table offsets on the device,
+  // size the table from the total (the one host read between the sweeps: 8 bytes), write the matches.
+  int find(const uint32_t* pattern, u32 n_chars, u32 flags) {
+    int r = set_device();
+    if (r) return r;
+    fd_valid = fd_pulled = false;
+    u64 n = enc_n;
+    if (!n) {
+      fd_valid = true;
+      return 0;
+    }
+    u8 pu[FD_PAT_W * 4u] = {};
+    u32 m_units = 0;  // in units of the encode
+    for (u32 j = 0; j < n_chars; j++) {
+      u32 c = pattern[j];
+      if (c - 0xD800u < 0x800u || c > 0x10FFFFu) c = 0xFFFDu;
+      if ((flags & FIND_ICASE) && c - 0x41u < 26u) c += 0x20u;
+      if (enc_mode == ENC_UTF8) {
+        if (c < 0x80u) {
+          pu[m_units++] = (u8)c;
+        } else if (c < 0x800u) {
+          pu[m_units++] = (u8)(0xC0u | (c >> 6));
+          pu[m_units++] = (u8)(0x80u | (c & 0x3Fu));
+        } else if (c < 0x10000u) {
+          pu[m_units++] = (u8)(0xE0u | (c >> 12));
+          pu[m_units++] = (u8)(0x80u | ((c >> 6) & 0x3Fu));
+          pu[m_units++] = (u8)(0x80u | (c & 0x3Fu));
+        } else {
+          pu[m_units++] = (u8)(0xF0u | (c >> 18));
+          pu[m_units++] = (u8)(0x80u | ((c >> 12) & 0x3Fu));
+          pu[m_units++] = (u8)(0x80u | ((c >> 6) & 0x3Fu));
+          pu[m_units++] = (u8)(0x80u | (c & 0x3Fu));
+        }
+      } else {
+        u16 w[2];
+        u32 k = 1;
+        if (c < 0x10000u) {
+          w[0] = (u16)c;
+        } else {
+          w[0] = (u16)(0xD800u + ((c - 0x10000u) >> 10));
+          w[1] = (u16)(0xDC00u + ((c - 0x10000u) & 0x3FFu));
+          k = 2;
+        }
+        memcpy(pu + 2u * m_units, w, 2u * k);
+        m_units += k;
+      }
+    }
+    memcpy(fd_pat_h, pu, sizeof(fd_pat_h));
+    if (n > fd_n_cap) {
+      HIPCHK(hipStreamSynchronize(stream));
+      dfree(fd_res);
+      fd_n_cap = 0;
+      HIPCHK(dalloc(fd_res, n));
+      fd_n_cap = n;
+    }
+    if (!fd_tot) HIPCHK(dalloc(fd_tot, 1));
+    if (!fd_pat) HIPCHK(dalloc(fd_pat, FD_PAT_W));
+    HIPCHK(hipMemcpyAsync(fd_pat, fd_pat_h, sizeof(fd_pat_h), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(ev_fd[0], stream));
+    EncIO ev = enc_view();
+    FdPat pt{fd_pat, m_units, flags & FIND_ICASE};
+    if (enc_mode == ENC_UTF8) hipLaunchKernelGGL(k_find_count<ENC_UTF8>, dim3((u32)n), dim3(LN_T), 0, stream, ev, fd_view(), pt, (u32)n);
+    else hipLaunchKernelGGL(k_find_count<ENC_UTF16>, dim3((u32)n), dim3(LN_T), 0, stream, ev, fd_view(), pt, (u32)n);
+    hipLaunchKernelGGL(k_find_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, fd_res, (u32)n, fd_tot);
+    HIPCHK(hipGetLastError());
+    u64 tot = 0;
+    HIPCHK(hipMemcpyAsync(&tot, fd_tot, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    r = diff_grow(fd_tab, fd_tab_cap, tot);
+    if (r) return r;
+    if (enc_mode == ENC_UTF8) hipLaunchKernelGGL(k_find_write<ENC_UTF8>, dim3((u32)n), dim3(LN_T), 0, stream, ev, fd_view(), pt, (u32)n);
+    else hipLaunchKernelGGL(k_find_write<ENC_UTF16>, dim3((u32)n), dim3(LN_T), 0, stream, ev, fd_view(), pt, (u32)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev_fd[1], stream));
+    fd_valid = true;
+    return 0;
+  }
+  // the per-index match counts and the device time of the last find, on the host (waits for it)
+  int fd_finish() {
+    if (!fd_valid) return CRDT_E_ARG;
+    if (fd_pulled) return 0;
+    int r = set_device();
+    if (r) return r;
+    fd_res_h.resize(enc_n);
+    last_fd_ms = 0;
+    if (enc_n) {
+      HIPCHK(hipMemcpyAsync(fd_res_h.data(), fd_res, enc_n * sizeof(FdRes), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, ev_fd[0], ev_fd[1]);
+      last_fd_ms = ms;
+    }
+    fd_pulled = true;
+    return 0;
+  }
 };
+static_assert(FIND_ICASE == CRDT_FIND_ASCII_ICASE && FD_MAX_CHARS == CRDT_FIND_MAX_CHARS, "CRDT_FIND_* are the kernels' flag and limit");
+static_assert(SEEK_NEXT == CRDT_SEEK_NEXT && SEEK_PREV == CRDT_SEEK_PREV, "CRDT_SEEK_* are the kernels' directions");
+static_assert(sizeof(Match) == sizeof(crdt_match) && sizeof(crdt_match) == 8, "crdt_match is the kernels' Match");
 static_assert(EOL_LF == CRDT_EOL_LF && EOL_ANY == CRDT_EOL_ANY, "CRDT_EOL_* are the kernels' modes");
 static_assert(COL_UNITS == CRDT_COL_UNITS && COL_CHARS == CRDT_COL_CHARS, "CRDT_COL_* are the kernels' column kinds");
 static_assert(sizeof(LineStart) == sizeof(crdt_line_start) && sizeof(crdt_line_start) == 8, "crdt_line_start is the kernels' LineStart");
@@ -1889,6 +2013,8 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   for (auto& x : e->ev_ln)
     if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
+  for (auto& x : e->ev_fd)
+    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
   *out = e.release();
   return 0;
 }
@@ -1909,6 +2035,8 @@ void crdt_engine_destroy(crdt_engine* e) {
   for (auto& x : e->ev_enc)
     if (x) (void)hipEventDestroy(x);
   for (auto& x : e->ev_ln)
+    if (x) (void)hipEventDestroy(x);
+  for (auto& x : e->ev_fd)
     if (x) (void)hipEventDestroy(x);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -2636,6 +2764,7 @@ uint64_t crdt_mem_bytes(const crdt_engine* e) {
          e->blame_run_cap * sizeof(BlameRun) + e->blame_n_cap * (4 + sizeof(BlameRes)) +
          e->enc_unit_cap + e->enc_sp_cap * 4 + e->enc_n_cap * (4 + 8 + sizeof(EncRes)) +
          e->ln_tab_cap * sizeof(LineStart) + e->ln_n_cap * sizeof(LnRes) +
+         e->fd_tab_cap * sizeof(Match) + e->fd_n_cap * sizeof(FdRes) + (e->fd_pat ? FD_PAT_W * 4u : 0u) +
          e->n_docs * (sizeof(DocState) + sizeof(DocSeg) + 4 + 4 + 8);
 }
 
@@ -2882,6 +3011,7 @@ int crdt_last_blame_ms(crdt_engine* e, double* ms) {
 int crdt_encode_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, int enc) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (e) e->ln_valid = e->ln_pulled = false;  // (a later encode call, successful or not, drops the line index)
+  if (e) e->fd_valid = e->fd_pulled = false;  // (... and the find result)
   if (!valid(e) || (n_docs && !docs) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
   if (enc != CRDT_ENC_UTF8 && enc != CRDT_ENC_UTF16) {
     g_last_error = "encode: enc is CRDT_ENC_UTF8 or CRDT_ENC_UTF16";
@@ -3200,6 +3330,127 @@ int crdt_linecol_to_pos(crdt_engine* e, uint64_t n, const uint32_t* idx, const u
   if (r) return r;
   HIPCHK(hipMemcpyAsync(pos, d_pos, n * 4, hipMemcpyDeviceToHost, e->stream));
   if (mid) HIPCHK(hipMemcpyAsync(mid, d_mid, n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int crdt_find_async(crdt_engine* e, const uint32_t* pattern, uint32_t n_chars, int flags) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  if (!pattern || n_chars == 0 || n_chars > CRDT_FIND_MAX_CHARS) {
+    g_last_error = "find: the pattern has 1 .. CRDT_FIND_MAX_CHARS code points";
+    return CRDT_E_ARG;
+  }
+  if (flags & ~CRDT_FIND_ASCII_ICASE) {
+    g_last_error = "find: flags is CRDT_FIND_EXACT or CRDT_FIND_ASCII_ICASE";
+    return CRDT_E_ARG;
+  }
+  int r = enc_query_ok(e);
+  if (r) return r;
+  g_alloc_oom = false;
+  r = e->find(pattern, n_chars, (u32)flags);
+  // (an allocation that fails leaves the engine as it was, with its encode result and its line index and without a find result)
+  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
+  return r;
+}
+
+static int fd_query_ok(crdt_engine* e) {
+  if (!e->fd_valid) {
+    g_last_error = "find: no find result (of the current encode result)";
+    return CRDT_E_ARG;
+  }
+  return 0;
+}
+static int seek_dir_ok(int dir) {
+  if (dir != CRDT_SEEK_NEXT && dir != CRDT_SEEK_PREV) {
+    g_last_error = "find: dir is CRDT_SEEK_NEXT or CRDT_SEEK_PREV";
+    return CRDT_E_ARG;
+  }
+  return 0;
+}
+// match count i of the last find, or nullptr (with the error text set) when the index has none
+static const FdRes* fd_result(crdt_engine* e, uint64_t i) {
+  if (i >= e->enc_n) return nullptr;
+  const FdRes& x = e->fd_res_h[i];
+  if (x.n_matches == INVALID) {
+    g_last_error = "find: the encode has no result for this index";
+    return nullptr;
+  }
+  return &x;
+}
+
+int crdt_find_counts(crdt_engine* e, uint32_t* n_matches) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = fd_query_ok(e);
+  if (r) return r;
+  r = e->fd_finish();
+  if (r) return r;
+  for (u64 i = 0; i < e->enc_n; i++)
+    if (n_matches) n_matches[i] = e->fd_res_h[i].n_matches;
+  return 0;
+}
+
+int crdt_find_read(crdt_engine* e, uint64_t i, crdt_match* matches) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = fd_query_ok(e);
+  if (r) return r;
+  r = e->fd_finish();
+  if (r) return r;
+  const FdRes* x = fd_result(e, i);
+  if (!x || (x->n_matches && !matches)) return CRDT_E_ARG;
+  if (x->n_matches) HIPCHK(hipMemcpy(matches, e->fd_tab + x->off, (u64)x->n_matches * sizeof(Match), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int crdt_last_find_ms(crdt_engine* e, double* ms) {
+  if (!e || !ms) return CRDT_E_ARG;
+  if (e->fd_valid && !e->fd_pulled) {
+    int r = e->fd_finish();
+    if (r) return r;
+  }
+  *ms = e->last_fd_ms;
+  return 0;
+}
+
+int crdt_find_seek_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, int dir, uint32_t* k) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = seek_dir_ok(dir);
+  if (r) return r;
+  r = fd_query_ok(e);
+  if (r) return r;
+  if (!n) return 0;
+  u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_find_seek, dim3(blocks), dim3(256), 0, e->stream, e->fd_view(), (u32)e->enc_n, n, idx, pos, (u32)dir, k);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int crdt_find_seek(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, int dir, uint32_t* k) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n && (!idx || !pos || !k))) return CRDT_E_ARG;
+  int r = seek_dir_ok(dir);
+  if (r) return r;
+  r = fd_query_ok(e);
+  if (r) return r;
+  r = e->fd_finish();
+  if (r) return r;
+  // the host form names only indexes that have a result (checked before anything is written)
+  for (uint64_t q = 0; q < n; q++)
+    if (!fd_result(e, idx[q])) return CRDT_E_ARG;
+  if (!n) return 0;
+  r = e->scratch(n * (4 + 4 + 4) + 64);
+  if (r) return r;
+  u32* d_idx = (u32*)e->qbuf;
+  u32* d_pos = d_idx + n;
+  u32* d_k = d_pos + n;
+  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(d_pos, pos, n * 4, hipMemcpyHostToDevice, e->stream));
+  r = crdt_find_seek_dev_async(e, n, d_idx, d_pos, dir, d_k);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(k, d_k, n * 4, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 }
