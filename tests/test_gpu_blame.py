@@ -1,4 +1,4 @@
-"""GPU checks of the authorship runs (crdt_blame_async: k_blame, k_blame_scan) through the C ABI.
+"""GPU checks of the authorship runs (crdt_blame_async: k_blame, k_result_scan<BlameRes>) through the C ABI.
 Every result must equal tests/blame_ref.py's ref_blame of the engine's own export exactly, so agent
 ids are the engine's.
 

@@ -1,5 +1,5 @@
 """GPU checks of documents at a past version (crdt_checkout_async: k_diff_mark, k_co_rank, k_co_count,
-k_co_scan, k_co_write; k_pos_to_loc_at / k_loc_to_pos_at) through the C ABI.  Every view must equal
+k_result_scan<CoRes>, k_co_write; k_pos_to_loc_at / k_loc_to_pos_at) through the C ABI.  Every view must equal
 tests/checkout_ref.py's ref_checkout of the engine's own export exactly; at versions that end a txn
 the text, its digest and the two mappings must equal an oracle replay of the history's prefix.
 

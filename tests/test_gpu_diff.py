@@ -1,4 +1,4 @@
-"""GPU checks of the per-document diff (crdt_diff_async: k_diff_mark, k_diff, k_diff_scan) through
+"""GPU checks of the per-document diff (crdt_diff_async: k_diff_mark, k_diff, k_result_scan<DiffRes>) through
 the C ABI.  Every result must equal tests/diff_ref.py's ref_diff of the engine's own export exactly;
 where content is set, the patches with their ins_text, applied to the oracle's text of the earlier
 version, must give the engine's current text.

@@ -1,4 +1,4 @@
-"""GPU checks of the encoded text and its unit offsets (crdt_encode_async: k_enc_count, k_enc_scan,
+"""GPU checks of the encoded text and its unit offsets (crdt_encode_async: k_enc_count, k_result_scan<EncRes>,
 k_enc_write; k_pos_to_units, k_units_to_pos) through the C ABI.  Every result must equal
 tests/encode_ref.py's ref_encode of the engine's own crdt_text exactly.
 

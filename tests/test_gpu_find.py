@@ -1,4 +1,4 @@
-"""GPU checks of find (crdt_find_async: k_find_count, k_find_scan, k_find_write; k_find_seek)
+"""GPU checks of find (crdt_find_async: k_find_count, k_result_scan<FdRes>, k_find_write; k_find_seek)
 through the C ABI.  Every result must equal tests/find_ref.py applied to the engine's own crdt_text
 exactly.
 

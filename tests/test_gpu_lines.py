@@ -1,4 +1,4 @@
-"""GPU checks of the line index (crdt_lines_async: k_ln_count, k_ln_scan, k_ln_write;
+"""GPU checks of the line index (crdt_lines_async: k_ln_count, k_result_scan<LnRes>, k_ln_write;
 k_pos_to_linecol, k_linecol_to_pos) through the C ABI.  Every result must equal tests/lines_ref.py
 applied to the engine's own crdt_text exactly.
 

@@ -28,7 +28,7 @@ constexpr u32 ENC_UTF8 = 0u, ENC_UTF16 = 1u;  // CRDT_ENC_*
 
 struct EncRes {
   u32 units, chars;  // both INVALID: no result for this index
-  u64 off;           // first unit of this index in the unit pool, in units (k_enc_scan)
+  u64 off;           // first unit of this index in the unit pool, in units (k_result_scan)
 };
 struct EncIO {
   const u32* docs;     // [i] the listed documents
@@ -139,35 +139,11 @@ __global__ __launch_bounds__(ENC_T) void k_enc_count(Pools P, TextIO T, EncIO E,
   }
 }
 
-// Exclusive scan of the indexes' unit counts into their offsets (k_co_scan's shape); *total =
-// units of all indexes.
-__global__ __launch_bounds__(DIFF_SCAN_T) void k_enc_scan(EncRes* res, u32 n, u64* total) {
-  __shared__ u64 s_a[DIFF_SCAN_T];
-  u32 t = threadIdx.x;
-  u32 per = (n + DIFF_SCAN_T - 1u) / DIFF_SCAN_T;
-  u64 lo = min((u64)t * per, (u64)n), hi = min(lo + per, (u64)n);
-  u64 a = 0;
-  for (u64 k = lo; k < hi; k++) a += res[k].units == INVALID ? 0u : res[k].units;
-  s_a[t] = a;
-  __syncthreads();
-  if (t == 0) {
-    a = 0;
-    for (u32 x = 0; x < DIFF_SCAN_T; x++) {
-      u64 p = s_a[x];
-      s_a[x] = a;
-      a += p;
-    }
-    *total = a;
-  }
-  __syncthreads();
-  a = s_a[t];
-  for (u64 k = lo; k < hi; k++) {
-    res[k].off = a;
-    a += res[k].units == INVALID ? 0u : res[k].units;
-  }
-}
+// k_result_scan's view of an EncRes: its units (an index without a result counts as 0)
+__device__ __forceinline__ void scan_counts(const EncRes& r, u64* c) { c[0] = r.units == INVALID ? 0u : r.units; }
+__device__ __forceinline__ void scan_store(EncRes& r, const u64* off) { r.off = off[0]; }
 
-// Second sweep, after k_enc_scan: the same passes and rows.  A wave's first unit is its sample; the
+// Second sweep, after k_result_scan: the same passes and rows.  A wave's first unit is its sample; the
 // row scans and the row totals before a row give every char its unit offset.  The pass's units (at
 // most 4,096 B) are assembled in LDS at the byte phase (0..3) their first byte has in the pool, and
 // go out as whole aligned dwords, coalesced.  A dword only partly inside the pass -- the first and

@@ -7,7 +7,6 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -77,6 +76,112 @@ void dfree(T*& p) {
   }
   p = nullptr;
 }
+
+// A device buffer that is kept and grown from call to call (contents not kept).  The stream is
+// drained before the old one goes: a previous call's kernels may still use it.  A failed
+// allocation leaves it empty, so the next call allocates again.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  u64 cap = 0;
+  int grow(hipStream_t stream, u64 need) {
+    if (p && need <= cap) return 0;
+    HIPCHK(hipStreamSynchronize(stream));
+    dfree(p);
+    cap = 0;
+    HIPCHK(dalloc(p, need));
+    cap = std::max<u64>(need, 1);
+    return 0;
+  }
+  void free() {
+    dfree(p);
+    cap = 0;
+  }
+  u64 bytes() const { return cap * sizeof(T); }
+};
+template <class... B>
+void free_bufs(B&... b) { (b.free(), ...); }
+template <class... B>
+u64 buf_bytes(const B&... b) { return (b.bytes() + ...); }
+
+// The lifetime of one result of the count / scan / write passes (diff, checkout, blame, encode,
+// lines, find): n per-index results of type Res (with their K totals, k_result_scan's) and the
+// device time between the two events.  `valid`: a call succeeded since the last drop(), so the
+// device holds a result; `pulled`: res_h and ms hold it too (finish()).  A call begins with
+// drop(), so one that fails anywhere leaves no result, and a buffer it could not allocate empty.
+template <class Res, u32 K = 1>
+struct ResultJob {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  u64 n = 0;
+  DevBuf<Res> res;
+  DevBuf<u64> tot;
+  u64 tot_h[K] = {};
+  std::vector<Res> res_h;
+  bool valid = false, pulled = false;
+  double ms = 0;
+
+  int create(int dev, hipStream_t s) {
+    device = dev;
+    stream = s;
+    for (auto& x : ev)
+      if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
+    return 0;
+  }
+  void destroy() {
+    for (auto& x : ev)
+      if (x) (void)hipEventDestroy(x);
+  }
+  void drop() { valid = pulled = false; }
+  void free() {
+    free_bufs(res, tot);
+    n = 0;
+    drop();
+  }
+  // a result of n_ indexes begins: its per-index results and totals (nothing to do for none)
+  int begin(u64 n_) {
+    drop();
+    n = n_;
+    if (!n) return 0;
+    int r = res.grow(stream, n);
+    return r ? r : tot.grow(stream, K);
+  }
+  int start() {
+    HIPCHK(hipEventRecord(ev[0], stream));
+    return 0;
+  }
+  // the one host read between the sweeps: the scan's totals into tot_h (waits for the first sweep)
+  int read_totals() {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(tot_h, tot.p, 8 * K, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  int stop() {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[1], stream));
+    valid = true;
+    return 0;
+  }
+  // the per-index results and the device time of the last call, on the host (waits for it)
+  int finish() {
+    if (!valid) return CRDT_E_ARG;
+    if (pulled) return 0;
+    HIPCHK(hipSetDevice(device));
+    res_h.resize(n);
+    ms = 0;
+    if (n) {
+      HIPCHK(hipMemcpyAsync(res_h.data(), res.p, n * sizeof(Res), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      float t = 0;
+      (void)hipEventElapsedTime(&t, ev[0], ev[1]);
+      ms = t;
+    }
+    pulled = true;
+    return 0;
+  }
+};
 
 // Relocatable per-document pools (sized by the per-document capacities).
 struct PoolSet {
@@ -263,111 +368,51 @@ struct crdt_engine {
   // query scratch
   void* qbuf = nullptr;
   u64 qbuf_bytes = 0;
+  // The six result passes (ResultJob above; DESIGN.md "Result jobs"), each with the buffers of its
+  // own next to it, all kept and grown from call to call.
   // diff (crdt_diff_async): the listed documents, their versions to diff from and bitmap bases
   // (host copies live until the next call: they are the source of asynchronous uploads), the
-  // "deleted before since" bitmaps, the per-index results and the result arrays; all kept and
-  // grown from call to call
-  hipEvent_t ev_diff[2] = {nullptr, nullptr};
+  // "deleted before since" bitmaps and the result arrays
+  ResultJob<DiffRes, 2> diff;
   std::vector<u32> diff_docs_h, diff_since_h;
   std::vector<u64> diff_bm_h;
-  std::vector<DiffRes> diff_res_h;
-  u32* diff_docs = nullptr;
-  u32* diff_since = nullptr;
-  u64* diff_bm_base = nullptr;
-  DiffRes* diff_res = nullptr;
-  u64* diff_tot = nullptr;
-  u32* diff_bm = nullptr;
-  Patch* diff_pat = nullptr;
-  u32* diff_io = nullptr;
-  u32* diff_it = nullptr;
-  u64 diff_n_cap = 0, diff_bm_cap = 0, diff_pat_cap = 0, diff_ins_cap = 0;
-  u64 diff_n = 0;
-  bool diff_valid = false;   // a diff result exists (crdt_diff_async succeeded since the last crdt_docs_alloc)
-  bool diff_pulled = false;  // ... and diff_res_h / last_diff_ms hold it
-  double last_diff_ms = 0;
-  // checkout (crdt_checkout_async): buffers of its own, kept and grown from call to call like the
-  // diff's.  The arrays are copies and stay readable; the _at queries also read the published
-  // index, so they need pub_epoch (counts publishes) unchanged and the index still current.
-  hipEvent_t ev_co[2] = {nullptr, nullptr};
+  DevBuf<u32> diff_docs, diff_since, diff_bm, diff_io, diff_it;
+  DevBuf<u64> diff_bm_base;
+  DevBuf<Patch> diff_pat;
+  // checkout (crdt_checkout_async).  The arrays are copies and stay readable; the _at queries also
+  // read the published index, so they need pub_epoch (counts publishes) unchanged and the index
+  // still current.
+  ResultJob<CoRes> co;
   std::vector<u32> co_docs_h, co_ver_h;
   std::vector<u64> co_bm_h, co_sp_h;
-  std::vector<CoRes> co_res_h;
-  u32* co_docs = nullptr;
-  u32* co_ver = nullptr;
-  u64* co_bm_base = nullptr;
-  u64* co_sp_base = nullptr;
-  CoRes* co_res = nullptr;
-  u64* co_tot = nullptr;
-  u32* co_bm = nullptr;
-  u32* co_rk = nullptr;
-  u32* co_opos = nullptr;
-  u32* co_ord = nullptr;
-  u32* co_text = nullptr;
-  u64 co_n_cap = 0, co_bm_cap = 0, co_rk_cap = 0, co_opos_cap = 0, co_out_cap = 0;
-  u64 co_n = 0;
-  bool co_valid = false;   // a checkout exists (crdt_checkout_async succeeded since the last crdt_docs_alloc)
-  bool co_pulled = false;  // ... and co_res_h / last_co_ms hold it
-  double last_co_ms = 0;
+  DevBuf<u32> co_docs, co_ver, co_bm, co_rk, co_opos, co_ord, co_text;
+  DevBuf<u64> co_bm_base, co_sp_base;
   u64 pub_epoch = 0, co_epoch = 0;
-  // authorship runs (crdt_blame_async): buffers of its own, kept and grown from call to call like
-  // the diff's; the result array is a copy and stays readable
-  hipEvent_t ev_blame[2] = {nullptr, nullptr};
+  // authorship runs (crdt_blame_async); the result array is a copy and stays readable
+  ResultJob<BlameRes> blame;
   std::vector<u32> blame_docs_h;
-  std::vector<BlameRes> blame_res_h;
-  u32* blame_docs = nullptr;
-  BlameRes* blame_res = nullptr;
-  u64* blame_tot = nullptr;
-  BlameRun* blame_runs = nullptr;
-  u64 blame_n_cap = 0, blame_run_cap = 0;
-  u64 blame_n = 0;
-  bool blame_valid = false;   // a blame result exists (crdt_blame_async succeeded since the last crdt_docs_alloc)
-  bool blame_pulled = false;  // ... and blame_res_h / last_blame_ms hold it
-  double last_blame_ms = 0;
-  // encoded text (crdt_encode_async): buffers of its own, kept and grown from call to call like
-  // the diff's.  The unit pool and its index (samples, per-index results) are copies: the queries
-  // read nothing else, so they stay valid whatever happens to the documents.
-  hipEvent_t ev_enc[2] = {nullptr, nullptr};
+  DevBuf<u32> blame_docs;
+  DevBuf<BlameRun> blame_runs;
+  // encoded text (crdt_encode_async).  The unit pool and its index (samples, per-index results)
+  // are copies: the queries read nothing else, so they stay valid whatever happens to the documents.
+  ResultJob<EncRes> enc;
   std::vector<u32> enc_docs_h;
   std::vector<u64> enc_sp_h;
-  std::vector<EncRes> enc_res_h;
-  u32* enc_docs = nullptr;
-  u64* enc_sp_base = nullptr;
-  EncRes* enc_res = nullptr;
-  u64* enc_tot = nullptr;
-  u32* enc_samples = nullptr;
-  u8* enc_units = nullptr;
-  u64 enc_n_cap = 0, enc_sp_cap = 0, enc_unit_cap = 0;  // (enc_unit_cap in bytes)
-  u64 enc_n = 0;
+  DevBuf<u32> enc_docs, enc_samples;
+  DevBuf<u64> enc_sp_base;
+  DevBuf<u8> enc_units;  // (ends on a dword: the queries read it a dword at a time)
   u32 enc_mode = 0;
-  bool enc_valid = false;   // an encode result exists (crdt_encode_async succeeded since the last crdt_docs_alloc)
-  bool enc_pulled = false;  // ... and enc_res_h / last_enc_ms hold it
-  double last_enc_ms = 0;
-  // line index (crdt_lines_async): belongs to the encode result it was built from (crdt_encode_async
-  // drops it: ln_valid implies enc_valid); buffers of its own, kept and grown from call to call like
-  // the encode's
-  hipEvent_t ev_ln[2] = {nullptr, nullptr};
-  std::vector<LnRes> ln_res_h;
-  LnRes* ln_res = nullptr;
-  u64* ln_tot = nullptr;
-  LineStart* ln_tab = nullptr;
-  u64 ln_n_cap = 0, ln_tab_cap = 0;
-  bool ln_valid = false;   // a line index of the current encode result exists
-  bool ln_pulled = false;  // ... and ln_res_h / last_ln_ms hold it
-  double last_ln_ms = 0;
-  // find result (crdt_find_async): belongs to the encode result it was built from, like the line
-  // index (crdt_encode_async drops it: fd_valid implies enc_valid); buffers of its own, kept and
-  // grown from call to call like the line index's
-  hipEvent_t ev_fd[2] = {nullptr, nullptr};
-  std::vector<FdRes> fd_res_h;
+  // line index (crdt_lines_async) and find result (crdt_find_async): each belongs to the encode
+  // result it was built from and takes its n from it (crdt_encode_async drops both: ln.valid and
+  // fd.valid imply enc.valid)
+  ResultJob<LnRes> ln;
+  DevBuf<LineStart> ln_tab;
+  ResultJob<FdRes> fd;
   u32 fd_pat_h[FD_PAT_W] = {};
-  u32* fd_pat = nullptr;  // FD_PAT_W dwords: the pattern's units
-  FdRes* fd_res = nullptr;
-  u64* fd_tot = nullptr;
-  Match* fd_tab = nullptr;
-  u64 fd_n_cap = 0, fd_tab_cap = 0;
-  bool fd_valid = false;   // a find result of the current encode result exists
-  bool fd_pulled = false;  // ... and fd_res_h / last_fd_ms hold it
-  double last_fd_ms = 0;
+  DevBuf<u32> fd_pat;  // FD_PAT_W dwords: the pattern's units
+  DevBuf<Match> fd_tab;
+  template <class F>
+  void each_job(F f) { f(diff); f(co); f(blame); f(enc); f(ln); f(fd); }
 
   Pools pools_view(const PoolSet& ps) const {
     Pools p{};
@@ -431,30 +476,10 @@ struct crdt_engine {
     if (qbuf) (void)hipFree(qbuf);
     qbuf = nullptr;
     qbuf_bytes = 0;
-    dfree(diff_docs); dfree(diff_since); dfree(diff_bm_base); dfree(diff_res); dfree(diff_tot); dfree(diff_bm);
-    dfree(diff_pat); dfree(diff_io); dfree(diff_it);
-    diff_n_cap = diff_bm_cap = diff_pat_cap = diff_ins_cap = 0;
-    diff_n = 0;
-    diff_valid = diff_pulled = false;
-    dfree(co_docs); dfree(co_ver); dfree(co_bm_base); dfree(co_sp_base); dfree(co_res); dfree(co_tot);
-    dfree(co_bm); dfree(co_rk); dfree(co_opos); dfree(co_ord); dfree(co_text);
-    co_n_cap = co_bm_cap = co_rk_cap = co_opos_cap = co_out_cap = 0;
-    co_n = 0;
-    co_valid = co_pulled = false;
-    dfree(blame_docs); dfree(blame_res); dfree(blame_tot); dfree(blame_runs);
-    blame_n_cap = blame_run_cap = 0;
-    blame_n = 0;
-    blame_valid = blame_pulled = false;
-    dfree(enc_docs); dfree(enc_sp_base); dfree(enc_res); dfree(enc_tot); dfree(enc_samples); dfree(enc_units);
-    enc_n_cap = enc_sp_cap = enc_unit_cap = 0;
-    enc_n = 0;
-    enc_valid = enc_pulled = false;
-    dfree(ln_res); dfree(ln_tot); dfree(ln_tab);
-    ln_n_cap = ln_tab_cap = 0;
-    ln_valid = ln_pulled = false;
-    dfree(fd_pat); dfree(fd_res); dfree(fd_tot); dfree(fd_tab);
-    fd_n_cap = fd_tab_cap = 0;
-    fd_valid = fd_pulled = false;
+    each_job([](auto& j) { j.free(); });
+    free_bufs(diff_docs, diff_since, diff_bm_base, diff_bm, diff_pat, diff_io, diff_it);
+    free_bufs(co_docs, co_ver, co_bm_base, co_sp_base, co_bm, co_rk, co_opos, co_ord, co_text);
+    free_bufs(blame_docs, blame_runs, enc_docs, enc_sp_base, enc_samples, enc_units, ln_tab, fd_pat, fd_tab);
   }
 
   int set_device() {
@@ -1370,45 +1395,41 @@ struct crdt_engine {
 
   DiffIO diff_view() const {
     DiffIO io{};
-    io.docs = diff_docs;
-    io.since = diff_since;
-    io.bm_base = diff_bm_base;
-    io.bm = diff_bm;
-    io.res = diff_res;
-    io.patches = diff_pat;
-    io.ins_order = diff_io;
-    io.ins_text = diff_it;
+    io.docs = diff_docs.p;
+    io.since = diff_since.p;
+    io.bm_base = diff_bm_base.p;
+    io.bm = diff_bm.p;
+    io.res = diff.res.p;
+    io.patches = diff_pat.p;
+    io.ins_order = diff_io.p;
+    io.ins_text = diff_it.p;
     io.content = content;
     io.cbase = cbase;
     io.clen = clen;
     return io;
   }
-  // A diff buffer for `need` entries (contents not kept).  The stream is drained before the old
-  // one goes: the previous diff's kernels may still use it.
-  template <class T>
-  int diff_grow(T*& p, u64& cap, u64 need) {
-    if (p && need <= cap) return 0;
-    HIPCHK(hipStreamSynchronize(stream));
-    dfree(p);
-    cap = 0;
-    HIPCHK(dalloc(p, need));
-    cap = std::max<u64>(need, 1);
-    return 0;
+  // buffers of `need` entries each (DevBuf::grow)
+  template <class... B>
+  int grow_bufs(u64 need, B&... b) {
+    int r = 0;
+    ((r = r ? r : b.grow(stream, need)), ...);
+    return r;
   }
   // crdt_diff_async: mark the deletes below each version, count every document's patches and
   // inserted items, scan the counts into offsets on the device, size the result arrays from the
   // two totals (the one host read between the passes: 16 bytes), write the results.
-  int diff(u64 n, const uint32_t* dl, const uint32_t* since) {
+  int run_diff(u64 n, const uint32_t* dl, const uint32_t* since) {
     int r = set_device();
     if (r) return r;
-    diff_valid = diff_pulled = false;
+    diff.drop();
     if (!published) {
       r = publish();
       if (r) return r;
     }
-    diff_n = n;
+    r = diff.begin(n);
+    if (r) return r;
     if (!n) {
-      diff_valid = true;
+      diff.valid = true;
       return 0;
     }
     diff_docs_h.assign(dl, dl + n);
@@ -1424,79 +1445,40 @@ struct crdt_engine {
       if (nw <= DIFF_MARK_WORDS) xw = std::max(xw, nw);
       else all_lds = false;
     }
-    if (n > diff_n_cap) {
-      HIPCHK(hipStreamSynchronize(stream));
-      dfree(diff_docs); dfree(diff_since); dfree(diff_bm_base); dfree(diff_res);
-      diff_n_cap = 0;
-      HIPCHK(dalloc(diff_docs, n));
-      HIPCHK(dalloc(diff_since, n));
-      HIPCHK(dalloc(diff_bm_base, n));
-      HIPCHK(dalloc(diff_res, n));
-      diff_n_cap = n;
-    }
-    if (!diff_tot) HIPCHK(dalloc(diff_tot, 2));
-    r = diff_grow(diff_bm, diff_bm_cap, words);
+    r = grow_bufs(n, diff_docs, diff_since, diff_bm_base);
+    if (!r) r = diff_bm.grow(stream, words);
     if (r) return r;
-    HIPCHK(hipMemcpyAsync(diff_docs, diff_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(diff_since, diff_since_h.data(), n * 4, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(diff_bm_base, diff_bm_h.data(), n * 8, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipEventRecord(ev_diff[0], stream));
-    if (!all_lds) HIPCHK(hipMemsetAsync(diff_bm, 0, words * 4, stream));
+    HIPCHK(hipMemcpyAsync(diff_docs.p, diff_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(diff_since.p, diff_since_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(diff_bm_base.p, diff_bm_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    r = diff.start();
+    if (r) return r;
+    if (!all_lds) HIPCHK(hipMemsetAsync(diff_bm.p, 0, words * 4, stream));
     Pools pv = pools_view(pools);
     PubOut ov = pub_view();
     hipLaunchKernelGGL(k_diff_mark, dim3((u32)n), dim3(DIFF_T), (size_t)xw * 4, stream, pv, diff_view(), (u32)n, xw);
     hipLaunchKernelGGL(k_diff<false>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, diff_view(), (u32)n);
-    hipLaunchKernelGGL(k_diff_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, diff_res, (u32)n, diff_tot);
-    HIPCHK(hipGetLastError());
-    u64 tot[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(tot, diff_tot, 16, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    r = diff_grow(diff_pat, diff_pat_cap, tot[0]);
+    hipLaunchKernelGGL(k_result_scan<DiffRes>, dim3(1), dim3(DIFF_SCAN_T), 0, stream, diff.res.p, (u32)n, diff.tot.p);
+    r = diff.read_totals();
+    if (!r) r = diff_pat.grow(stream, diff.tot_h[0]);
+    if (!r) r = grow_bufs(diff.tot_h[1], diff_io, diff_it);
     if (r) return r;
-    if (!diff_io || !diff_it || tot[1] > diff_ins_cap) {
-      dfree(diff_io); dfree(diff_it);
-      diff_ins_cap = 0;
-      HIPCHK(dalloc(diff_io, tot[1]));
-      HIPCHK(dalloc(diff_it, tot[1]));
-      diff_ins_cap = std::max<u64>(tot[1], 1);
-    }
     hipLaunchKernelGGL(k_diff<true>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, diff_view(), (u32)n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_diff[1], stream));
-    diff_valid = true;
-    return 0;
-  }
-  // the per-index results and the device time of the last diff, on the host (waits for it)
-  int diff_finish() {
-    if (!diff_valid) return CRDT_E_ARG;
-    if (diff_pulled) return 0;
-    int r = set_device();
-    if (r) return r;
-    diff_res_h.resize(diff_n);
-    last_diff_ms = 0;
-    if (diff_n) {
-      HIPCHK(hipMemcpyAsync(diff_res_h.data(), diff_res, diff_n * sizeof(DiffRes), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev_diff[0], ev_diff[1]);
-      last_diff_ms = ms;
-    }
-    diff_pulled = true;
-    return 0;
+    return diff.stop();
   }
 
   CoIO co_view() const {
     CoIO io{};
-    io.docs = co_docs;
-    io.version = co_ver;
-    io.bm_base = co_bm_base;
-    io.bm = co_bm;
-    io.rk = co_rk;
-    io.sp_base = co_sp_base;
-    io.opos = co_opos;
-    io.res = co_res;
-    io.ord = co_ord;
-    io.text = co_text;
+    io.docs = co_docs.p;
+    io.version = co_ver.p;
+    io.bm_base = co_bm_base.p;
+    io.bm = co_bm.p;
+    io.rk = co_rk.p;
+    io.sp_base = co_sp_base.p;
+    io.opos = co_opos.p;
+    io.res = co.res.p;
+    io.ord = co_ord.p;
+    io.text = co_text.p;
     io.content = content;
     io.cbase = cbase;
     io.clen = clen;
@@ -1506,18 +1488,19 @@ struct crdt_engine {
   // buffers), rank the bitmaps, count every view's items per span (opos) and in all, scan the
   // lengths into offsets on the device, size the two item arrays from the total (the one host read:
   // 8 bytes), write the items.
-  int checkout(u64 n, const uint32_t* dl, const uint32_t* ver) {
+  int run_checkout(u64 n, const uint32_t* dl, const uint32_t* ver) {
     int r = set_device();
     if (r) return r;
-    co_valid = co_pulled = false;
+    co.drop();
     if (!published) {
       r = publish();
       if (r) return r;
     }
-    co_n = n;
     co_epoch = pub_epoch;
+    r = co.begin(n);
+    if (r) return r;
     if (!n) {
-      co_valid = true;
+      co.valid = true;
       return 0;
     }
     co_docs_h.assign(dl, dl + n);
@@ -1536,173 +1519,103 @@ struct crdt_engine {
       if (nw <= DIFF_MARK_WORDS) xw = std::max(xw, nw);
       else all_lds = false;
     }
-    if (n > co_n_cap) {
-      HIPCHK(hipStreamSynchronize(stream));
-      dfree(co_docs); dfree(co_ver); dfree(co_bm_base); dfree(co_sp_base); dfree(co_res);
-      co_n_cap = 0;
-      HIPCHK(dalloc(co_docs, n));
-      HIPCHK(dalloc(co_ver, n));
-      HIPCHK(dalloc(co_bm_base, n));
-      HIPCHK(dalloc(co_sp_base, n));
-      HIPCHK(dalloc(co_res, n));
-      co_n_cap = n;
-    }
-    if (!co_tot) HIPCHK(dalloc(co_tot, 1));
-    r = diff_grow(co_bm, co_bm_cap, words);
+    r = grow_bufs(n, co_docs, co_ver, co_bm_base, co_sp_base);
+    if (!r) r = grow_bufs(words, co_bm, co_rk);
+    if (!r) r = co_opos.grow(stream, spans);
     if (r) return r;
-    r = diff_grow(co_rk, co_rk_cap, words);
+    HIPCHK(hipMemcpyAsync(co_docs.p, co_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(co_ver.p, co_ver_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(co_bm_base.p, co_bm_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(co_sp_base.p, co_sp_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    r = co.start();
     if (r) return r;
-    r = diff_grow(co_opos, co_opos_cap, spans);
-    if (r) return r;
-    HIPCHK(hipMemcpyAsync(co_docs, co_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(co_ver, co_ver_h.data(), n * 4, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(co_bm_base, co_bm_h.data(), n * 8, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(co_sp_base, co_sp_h.data(), n * 8, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipEventRecord(ev_co[0], stream));
-    if (!all_lds) HIPCHK(hipMemsetAsync(co_bm, 0, words * 4, stream));
+    if (!all_lds) HIPCHK(hipMemsetAsync(co_bm.p, 0, words * 4, stream));
     Pools pv = pools_view(pools);
     PubOut ov = pub_view();
     DiffIO mark{};  // k_diff_mark reads these four only
-    mark.docs = co_docs;
-    mark.since = co_ver;
-    mark.bm_base = co_bm_base;
-    mark.bm = co_bm;
+    mark.docs = co_docs.p;
+    mark.since = co_ver.p;
+    mark.bm_base = co_bm_base.p;
+    mark.bm = co_bm.p;
     hipLaunchKernelGGL(k_diff_mark, dim3((u32)n), dim3(DIFF_T), (size_t)xw * 4, stream, pv, mark, (u32)n, xw);
     hipLaunchKernelGGL(k_co_rank, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, co_view(), (u32)n);
     hipLaunchKernelGGL(k_co_count, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, co_view(), (u32)n);
-    hipLaunchKernelGGL(k_co_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, co_res, (u32)n, co_tot);
-    HIPCHK(hipGetLastError());
-    u64 tot = 0;
-    HIPCHK(hipMemcpyAsync(&tot, co_tot, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (!co_ord || !co_text || tot > co_out_cap) {
-      dfree(co_ord); dfree(co_text);
-      co_out_cap = 0;
-      HIPCHK(dalloc(co_ord, tot));
-      HIPCHK(dalloc(co_text, tot));
-      co_out_cap = std::max<u64>(tot, 1);
-    }
-    hipLaunchKernelGGL(k_co_write, dim3((u32)n), dim3(64 * CO_WAVES), 0, stream, pv, ov, co_view(), (u32)n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_co[1], stream));
-    co_valid = true;
-    return 0;
-  }
-  // the per-index results and the device time of the last checkout, on the host (waits for it)
-  int co_finish() {
-    if (!co_valid) return CRDT_E_ARG;
-    if (co_pulled) return 0;
-    int r = set_device();
+    hipLaunchKernelGGL(k_result_scan<CoRes>, dim3(1), dim3(DIFF_SCAN_T), 0, stream, co.res.p, (u32)n, co.tot.p);
+    r = co.read_totals();
+    if (!r) r = grow_bufs(co.tot_h[0], co_ord, co_text);
     if (r) return r;
-    co_res_h.resize(co_n);
-    last_co_ms = 0;
-    if (co_n) {
-      HIPCHK(hipMemcpyAsync(co_res_h.data(), co_res, co_n * sizeof(CoRes), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev_co[0], ev_co[1]);
-      last_co_ms = ms;
-    }
-    co_pulled = true;
-    return 0;
+    hipLaunchKernelGGL(k_co_write, dim3((u32)n), dim3(64 * CO_WAVES), 0, stream, pv, ov, co_view(), (u32)n);
+    return co.stop();
   }
   // the _at queries' precondition: a checkout whose published index is still the current one
-  bool co_fresh() const { return co_valid && published && co_epoch == pub_epoch; }
+  bool co_fresh() const { return co.valid && published && co_epoch == pub_epoch; }
 
   BlameIO blame_view() const {
     BlameIO io{};
-    io.docs = blame_docs;
-    io.res = blame_res;
-    io.runs = blame_runs;
+    io.docs = blame_docs.p;
+    io.res = blame.res.p;
+    io.runs = blame_runs.p;
     return io;
   }
   // crdt_blame_async: count every listed document's runs, scan the counts into offsets on the
   // device, size the result array from the total (the one host read between the sweeps: 8 bytes),
   // write the runs.
-  int blame(u64 n, const uint32_t* dl, u32 mode) {
+  int run_blame(u64 n, const uint32_t* dl, u32 mode) {
     int r = set_device();
     if (r) return r;
-    blame_valid = blame_pulled = false;
+    blame.drop();
     if (!published) {
       r = publish();
       if (r) return r;
     }
-    blame_n = n;
+    r = blame.begin(n);
+    if (r) return r;
     if (!n) {
-      blame_valid = true;
+      blame.valid = true;
       return 0;
     }
     blame_docs_h.assign(dl, dl + n);
-    if (n > blame_n_cap) {
-      HIPCHK(hipStreamSynchronize(stream));
-      dfree(blame_docs); dfree(blame_res);
-      blame_n_cap = 0;
-      HIPCHK(dalloc(blame_docs, n));
-      HIPCHK(dalloc(blame_res, n));
-      blame_n_cap = n;
-    }
-    if (!blame_tot) HIPCHK(dalloc(blame_tot, 1));
-    HIPCHK(hipMemcpyAsync(blame_docs, blame_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipEventRecord(ev_blame[0], stream));
+    r = blame_docs.grow(stream, n);
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(blame_docs.p, blame_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    r = blame.start();
+    if (r) return r;
     Pools pv = pools_view(pools);
     PubOut ov = pub_view();
     hipLaunchKernelGGL(k_blame<false>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, blame_view(), (u32)n, mode);
-    hipLaunchKernelGGL(k_blame_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, blame_res, (u32)n, blame_tot);
-    HIPCHK(hipGetLastError());
-    u64 tot = 0;
-    HIPCHK(hipMemcpyAsync(&tot, blame_tot, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    r = diff_grow(blame_runs, blame_run_cap, tot);
+    hipLaunchKernelGGL(k_result_scan<BlameRes>, dim3(1), dim3(DIFF_SCAN_T), 0, stream, blame.res.p, (u32)n, blame.tot.p);
+    r = blame.read_totals();
+    if (!r) r = blame_runs.grow(stream, blame.tot_h[0]);
     if (r) return r;
     hipLaunchKernelGGL(k_blame<true>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, blame_view(), (u32)n, mode);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_blame[1], stream));
-    blame_valid = true;
-    return 0;
-  }
-  // the per-index results and the device time of the last blame, on the host (waits for it)
-  int blame_finish() {
-    if (!blame_valid) return CRDT_E_ARG;
-    if (blame_pulled) return 0;
-    int r = set_device();
-    if (r) return r;
-    blame_res_h.resize(blame_n);
-    last_blame_ms = 0;
-    if (blame_n) {
-      HIPCHK(hipMemcpyAsync(blame_res_h.data(), blame_res, blame_n * sizeof(BlameRes), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev_blame[0], ev_blame[1]);
-      last_blame_ms = ms;
-    }
-    blame_pulled = true;
-    return 0;
+    return blame.stop();
   }
 
   EncIO enc_view() const {
     EncIO io{};
-    io.docs = enc_docs;
-    io.sp_base = enc_sp_base;
-    io.res = enc_res;
-    io.samples = enc_samples;
-    io.units = enc_units;
+    io.docs = enc_docs.p;
+    io.sp_base = enc_sp_base.p;
+    io.res = enc.res.p;
+    io.samples = enc_samples.p;
+    io.units = enc_units.p;
     return io;
   }
   // crdt_encode_async: count every listed document's units (and write its samples), scan the
   // counts into offsets on the device, size the unit pool from the total (the one host read between
   // the sweeps: 8 bytes), write the units.
-  int encode(u64 n, const uint32_t* dl, u32 enc) {
+  int run_encode(u64 n, const uint32_t* dl, u32 mode) {
     int r = set_device();
     if (r) return r;
-    enc_valid = enc_pulled = false;
+    enc.drop();
     if (!materialized) {
       r = materialize();
       if (r) return r;
     }
-    enc_n = n;
-    enc_mode = enc;
+    enc_mode = mode;
+    r = enc.begin(n);
+    if (r) return r;
     if (!n) {
-      enc_valid = true;
+      enc.valid = true;
       return 0;
     }
     enc_docs_h.assign(dl, dl + n);
@@ -1712,86 +1625,49 @@ struct crdt_engine {
       enc_sp_h[i] = n_samples;
       n_samples += seg_h[dl[i]].ord_cap / ENC_S + 1u;
     }
-    if (n > enc_n_cap) {
-      HIPCHK(hipStreamSynchronize(stream));
-      dfree(enc_docs); dfree(enc_sp_base); dfree(enc_res);
-      enc_n_cap = 0;
-      HIPCHK(dalloc(enc_docs, n));
-      HIPCHK(dalloc(enc_sp_base, n));
-      HIPCHK(dalloc(enc_res, n));
-      enc_n_cap = n;
-    }
-    if (!enc_tot) HIPCHK(dalloc(enc_tot, 1));
-    r = diff_grow(enc_samples, enc_sp_cap, n_samples);
+    r = enc_docs.grow(stream, n);
+    if (!r) r = enc_sp_base.grow(stream, n);
+    if (!r) r = enc_samples.grow(stream, n_samples);
     if (r) return r;
-    HIPCHK(hipMemcpyAsync(enc_docs, enc_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(enc_sp_base, enc_sp_h.data(), n * 8, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipEventRecord(ev_enc[0], stream));
+    HIPCHK(hipMemcpyAsync(enc_docs.p, enc_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(enc_sp_base.p, enc_sp_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    r = enc.start();
+    if (r) return r;
     Pools pv = pools_view(pools);
     TextIO tv = text_view();
-    if (enc == ENC_UTF8) hipLaunchKernelGGL(k_enc_count<ENC_UTF8>, dim3((u32)n), dim3(ENC_T), 0, stream, pv, tv, enc_view(), (u32)n);
+    if (mode == ENC_UTF8) hipLaunchKernelGGL(k_enc_count<ENC_UTF8>, dim3((u32)n), dim3(ENC_T), 0, stream, pv, tv, enc_view(), (u32)n);
     else hipLaunchKernelGGL(k_enc_count<ENC_UTF16>, dim3((u32)n), dim3(ENC_T), 0, stream, pv, tv, enc_view(), (u32)n);
-    hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, enc_res, (u32)n, enc_tot);
-    HIPCHK(hipGetLastError());
-    u64 tot = 0;
-    HIPCHK(hipMemcpyAsync(&tot, enc_tot, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    hipLaunchKernelGGL(k_result_scan<EncRes>, dim3(1), dim3(DIFF_SCAN_T), 0, stream, enc.res.p, (u32)n, enc.tot.p);
+    r = enc.read_totals();
     // (the pool ends on a dword: the queries read it a dword at a time)
-    r = diff_grow(enc_units, enc_unit_cap, (tot * (enc == ENC_UTF8 ? 1u : 2u) + 3u) / 4u * 4u);
+    if (!r) r = enc_units.grow(stream, (enc.tot_h[0] * (mode == ENC_UTF8 ? 1u : 2u) + 3u) / 4u * 4u);
     if (r) return r;
-    if (enc == ENC_UTF8) hipLaunchKernelGGL(k_enc_write<ENC_UTF8>, dim3((u32)n), dim3(ENC_T), 0, stream, pv, tv, enc_view(), (u32)n);
+    if (mode == ENC_UTF8) hipLaunchKernelGGL(k_enc_write<ENC_UTF8>, dim3((u32)n), dim3(ENC_T), 0, stream, pv, tv, enc_view(), (u32)n);
     else hipLaunchKernelGGL(k_enc_write<ENC_UTF16>, dim3((u32)n), dim3(ENC_T), 0, stream, pv, tv, enc_view(), (u32)n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_enc[1], stream));
-    enc_valid = true;
-    return 0;
-  }
-  // the per-index results and the device time of the last encode, on the host (waits for it)
-  int enc_finish() {
-    if (!enc_valid) return CRDT_E_ARG;
-    if (enc_pulled) return 0;
-    int r = set_device();
-    if (r) return r;
-    enc_res_h.resize(enc_n);
-    last_enc_ms = 0;
-    if (enc_n) {
-      HIPCHK(hipMemcpyAsync(enc_res_h.data(), enc_res, enc_n * sizeof(EncRes), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev_enc[0], ev_enc[1]);
-      last_enc_ms = ms;
-    }
-    enc_pulled = true;
-    return 0;
+    return enc.stop();
   }
 
   LnIO ln_view() const {
     LnIO io{};
-    io.res = ln_res;
-    io.tab = ln_tab;
+    io.res = ln.res.p;
+    io.tab = ln_tab.p;
     return io;
   }
   // crdt_lines_async: count every index's breaks over its units of the pool, scan the counts into
   // table offsets on the device, size the table from the total (the one host read between the
   // sweeps: 8 bytes), write the line starts.
-  int lines(u32 eol) {
+  int run_lines(u32 eol) {
     int r = set_device();
     if (r) return r;
-    ln_valid = ln_pulled = false;
-    u64 n = enc_n;
+    u64 n = enc.n;
+    r = ln.begin(n);
+    if (r) return r;
     if (!n) {
-      ln_valid = true;
+      ln.valid = true;
       return 0;
     }
-    if (n > ln_n_cap) {
-      HIPCHK(hipStreamSynchronize(stream));
-      dfree(ln_res);
-      ln_n_cap = 0;
-      HIPCHK(dalloc(ln_res, n));
-      ln_n_cap = n;
-    }
-    if (!ln_tot) HIPCHK(dalloc(ln_tot, 1));
-    HIPCHK(hipEventRecord(ev_ln[0], stream));
+    r = ln.start();
+    if (r) return r;
     EncIO ev = enc_view();
     u32 inst = enc_mode * 2u + eol;
     switch (inst) {
@@ -1800,12 +1676,9 @@ struct crdt_engine {
       case 2: hipLaunchKernelGGL((k_ln_count<ENC_UTF16, EOL_LF>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
       default: hipLaunchKernelGGL((k_ln_count<ENC_UTF16, EOL_ANY>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
     }
-    hipLaunchKernelGGL(k_ln_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, ln_res, (u32)n, ln_tot);
-    HIPCHK(hipGetLastError());
-    u64 tot = 0;
-    HIPCHK(hipMemcpyAsync(&tot, ln_tot, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    r = diff_grow(ln_tab, ln_tab_cap, tot);
+    hipLaunchKernelGGL(k_result_scan<LnRes>, dim3(1), dim3(DIFF_SCAN_T), 0, stream, ln.res.p, (u32)n, ln.tot.p);
+    r = ln.read_totals();
+    if (!r) r = ln_tab.grow(stream, ln.tot_h[0]);
     if (r) return r;
     switch (inst) {
       case 0: hipLaunchKernelGGL((k_ln_write<ENC_UTF8, EOL_LF>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
@@ -1813,46 +1686,26 @@ struct crdt_engine {
       case 2: hipLaunchKernelGGL((k_ln_write<ENC_UTF16, EOL_LF>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
       default: hipLaunchKernelGGL((k_ln_write<ENC_UTF16, EOL_ANY>), dim3((u32)n), dim3(LN_T), 0, stream, ev, ln_view(), (u32)n); break;
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_ln[1], stream));
-    ln_valid = true;
-    return 0;
-  }
-  // the per-index line counts and the device time of the last line index, on the host (waits for it)
-  int ln_finish() {
-    if (!ln_valid) return CRDT_E_ARG;
-    if (ln_pulled) return 0;
-    int r = set_device();
-    if (r) return r;
-    ln_res_h.resize(enc_n);
-    last_ln_ms = 0;
-    if (enc_n) {
-      HIPCHK(hipMemcpyAsync(ln_res_h.data(), ln_res, enc_n * sizeof(LnRes), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev_ln[0], ev_ln[1]);
-      last_ln_ms = ms;
-    }
-    ln_pulled = true;
-    return 0;
+    return ln.stop();
   }
 
   FdIO fd_view() const {
     FdIO io{};
-    io.res = fd_res;
-    io.tab = fd_tab;
+    io.res = fd.res.p;
+    io.tab = fd_tab.p;
     return io;
   }
   // crdt_find_async: sanitise, fold and encode the pattern into the encode's units, count every
   // index's matches over its units of the pool, scan the counts into table offsets on the device,
   // size the table from the total (the one host read between the sweeps: 8 bytes), write the matches.
-  int find(const uint32_t* pattern, u32 n_chars, u32 flags) {
+  int run_find(const uint32_t* pattern, u32 n_chars, u32 flags) {
     int r = set_device();
     if (r) return r;
-    fd_valid = fd_pulled = false;
-    u64 n = enc_n;
+    u64 n = enc.n;
+    r = fd.begin(n);
+    if (r) return r;
     if (!n) {
-      fd_valid = true;
+      fd.valid = true;
       return 0;
     }
     u8 pu[FD_PAT_W * 4u] = {};
@@ -1892,52 +1745,22 @@ struct crdt_engine {
       }
     }
     memcpy(fd_pat_h, pu, sizeof(fd_pat_h));
-    if (n > fd_n_cap) {
-      HIPCHK(hipStreamSynchronize(stream));
-      dfree(fd_res);
-      fd_n_cap = 0;
-      HIPCHK(dalloc(fd_res, n));
-      fd_n_cap = n;
-    }
-    if (!fd_tot) HIPCHK(dalloc(fd_tot, 1));
-    if (!fd_pat) HIPCHK(dalloc(fd_pat, FD_PAT_W));
-    HIPCHK(hipMemcpyAsync(fd_pat, fd_pat_h, sizeof(fd_pat_h), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipEventRecord(ev_fd[0], stream));
+    r = fd_pat.grow(stream, FD_PAT_W);
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(fd_pat.p, fd_pat_h, sizeof(fd_pat_h), hipMemcpyHostToDevice, stream));
+    r = fd.start();
+    if (r) return r;
     EncIO ev = enc_view();
-    FdPat pt{fd_pat, m_units, flags & FIND_ICASE};
+    FdPat pt{fd_pat.p, m_units, flags & FIND_ICASE};
     if (enc_mode == ENC_UTF8) hipLaunchKernelGGL(k_find_count<ENC_UTF8>, dim3((u32)n), dim3(LN_T), 0, stream, ev, fd_view(), pt, (u32)n);
     else hipLaunchKernelGGL(k_find_count<ENC_UTF16>, dim3((u32)n), dim3(LN_T), 0, stream, ev, fd_view(), pt, (u32)n);
-    hipLaunchKernelGGL(k_find_scan, dim3(1), dim3(DIFF_SCAN_T), 0, stream, fd_res, (u32)n, fd_tot);
-    HIPCHK(hipGetLastError());
-    u64 tot = 0;
-    HIPCHK(hipMemcpyAsync(&tot, fd_tot, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    r = diff_grow(fd_tab, fd_tab_cap, tot);
+    hipLaunchKernelGGL(k_result_scan<FdRes>, dim3(1), dim3(DIFF_SCAN_T), 0, stream, fd.res.p, (u32)n, fd.tot.p);
+    r = fd.read_totals();
+    if (!r) r = fd_tab.grow(stream, fd.tot_h[0]);
     if (r) return r;
     if (enc_mode == ENC_UTF8) hipLaunchKernelGGL(k_find_write<ENC_UTF8>, dim3((u32)n), dim3(LN_T), 0, stream, ev, fd_view(), pt, (u32)n);
     else hipLaunchKernelGGL(k_find_write<ENC_UTF16>, dim3((u32)n), dim3(LN_T), 0, stream, ev, fd_view(), pt, (u32)n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev_fd[1], stream));
-    fd_valid = true;
-    return 0;
-  }
-  // the per-index match counts and the device time of the last find, on the host (waits for it)
-  int fd_finish() {
-    if (!fd_valid) return CRDT_E_ARG;
-    if (fd_pulled) return 0;
-    int r = set_device();
-    if (r) return r;
-    fd_res_h.resize(enc_n);
-    last_fd_ms = 0;
-    if (enc_n) {
-      HIPCHK(hipMemcpyAsync(fd_res_h.data(), fd_res, enc_n * sizeof(FdRes), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev_fd[0], ev_fd[1]);
-      last_fd_ms = ms;
-    }
-    fd_pulled = true;
-    return 0;
+    return fd.stop();
   }
 };
 static_assert(FIND_ICASE == CRDT_FIND_ASCII_ICASE && FD_MAX_CHARS == CRDT_FIND_MAX_CHARS, "CRDT_FIND_* are the kernels' flag and limit");
@@ -1968,6 +1791,77 @@ static bool ids_ok(const crdt_engine* e, uint64_t n, const uint32_t* docs) {
   return true;
 }
 
+// A result call that allocates: out of device memory is CRDT_E_NOMEM.  (No relayout is involved:
+// an allocation that fails leaves the engine as it was, without that call's result.)
+template <class F>
+static int oom_as_nomem(F call) {
+  g_alloc_oom = false;
+  int r = call();
+  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
+  return r;
+}
+
+// crdt_last_*_ms: the device time of a job's last call (waits for it)
+template <class J>
+static int job_ms(crdt_engine* e, J crdt_engine::*job, double* ms) {
+  if (!e || !ms) return CRDT_E_ARG;
+  J& j = e->*job;
+  if (j.valid && !j.pulled) {
+    int r = j.finish();
+    if (r) return r;
+  }
+  *ms = j.ms;
+  return 0;
+}
+
+// Staging of a host-form query's n-element arrays in the engine's scratch: reserve() once for the
+// bytes of one query, then in() / out() place the arrays one after the other in declaration order
+// (so declare the widest element types first: u32, then u16, then u8, and every array is aligned)
+// and return their device addresses; in() queues the upload, finish() queues the outputs'
+// downloads after the query's kernels and waits for them.
+struct QStage {
+  crdt_engine* e;
+  u64 n;
+  char *at = nullptr, *end = nullptr;
+  int err = 0;
+  struct Out { void* host; const void* dev; u64 bytes; } outs[4];
+  u32 n_out = 0;
+  int reserve(u64 bytes_per_query) {
+    int r = e->scratch(n * bytes_per_query + 64);
+    at = (char*)e->qbuf;
+    end = at + n * bytes_per_query;
+    return r;
+  }
+  template <class T>
+  T* take() {
+    if ((u64)(end - at) < n * sizeof(T)) err = CRDT_E_ARG;  // (more arrays than were reserved: a bug here)
+    T* d = err ? nullptr : (T*)at;
+    at += n * sizeof(T);
+    return d;
+  }
+  int upload(void* d, const void* host, u64 bytes) {
+    HIPCHK(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, e->stream));
+    return 0;
+  }
+  template <class T>
+  T* in(const T* host) {
+    T* d = take<T>();
+    if (!err) err = upload(d, host, n * sizeof(T));
+    return d;
+  }
+  template <class T>
+  T* out(T* host) {  // (an optional output the caller did not ask for keeps its place and is not copied)
+    T* d = take<T>();
+    if (host && !err) outs[n_out++] = Out{host, d, n * sizeof(T)};
+    return d;
+  }
+  int finish() {
+    for (u32 k = 0; k < n_out; k++) HIPCHK(hipMemcpyAsync(outs[k].host, outs[k].dev, outs[k].bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
+  }
+};
+
 extern "C" {
 
 int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
@@ -1978,11 +1872,18 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) return CRDT_E_DEVICE;
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return CRDT_E_DEVICE;
-  std::unique_ptr<crdt_engine> e(new crdt_engine());
+  crdt_engine* e = new crdt_engine();
   e->L = cfg->leaf_cap;
   e->device = cfg->device;
-  if (hipSetDevice(e->device) != hipSuccess) return CRDT_E_DEVICE;
-  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) return CRDT_E_DEVICE;
+  // (a failure from here on goes through crdt_engine_destroy: the stream and the events made so
+  // far are released with the struct)
+  bool ok = hipSetDevice(e->device) == hipSuccess && hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) == hipSuccess;
+  for (auto& x : e->ev) ok = ok && hipEventCreate(&x) == hipSuccess;
+  e->each_job([&](auto& j) { ok = ok && j.create(e->device, e->stream) == 0; });
+  if (!ok) {
+    crdt_engine_destroy(e);
+    return CRDT_E_DEVICE;
+  }
   // the replay's LDS root may take a workgroup's whole 160 KiB (one wave per workgroup)
   (void)hipFuncSetAttribute((const void*)k_replay<32, SHAPE_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
   (void)hipFuncSetAttribute((const void*)k_replay<4, SHAPE_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
@@ -2001,21 +1902,7 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
   (void)hipFuncSetAttribute((const void*)k_pub_index, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)pubx_lds_bytes(PUBX_MAX_WORDS));
   (void)hipFuncSetAttribute((const void*)k_diff_mark, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIFF_MARK_WORDS * 4u));
-  for (auto& x : e->ev)
-    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
-  for (auto& x : e->ev_diff)
-    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
-  for (auto& x : e->ev_co)
-    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
-  for (auto& x : e->ev_blame)
-    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
-  for (auto& x : e->ev_enc)
-    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
-  for (auto& x : e->ev_ln)
-    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
-  for (auto& x : e->ev_fd)
-    if (hipEventCreate(&x) != hipSuccess) return CRDT_E_DEVICE;
-  *out = e.release();
+  *out = e;
   return 0;
 }
 
@@ -2026,18 +1913,7 @@ void crdt_engine_destroy(crdt_engine* e) {
   e->release();
   for (auto& x : e->ev)
     if (x) (void)hipEventDestroy(x);
-  for (auto& x : e->ev_diff)
-    if (x) (void)hipEventDestroy(x);
-  for (auto& x : e->ev_co)
-    if (x) (void)hipEventDestroy(x);
-  for (auto& x : e->ev_blame)
-    if (x) (void)hipEventDestroy(x);
-  for (auto& x : e->ev_enc)
-    if (x) (void)hipEventDestroy(x);
-  for (auto& x : e->ev_ln)
-    if (x) (void)hipEventDestroy(x);
-  for (auto& x : e->ev_fd)
-    if (x) (void)hipEventDestroy(x);
+  e->each_job([](auto& j) { j.destroy(); });
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -2577,22 +2453,16 @@ int crdt_pos_to_loc(crdt_engine* e, uint64_t n, const uint32_t* doc, const uint3
   if (!n) return 0;
   int r = e->ensure_published();
   if (r) return r;
-  u64 bytes = n * (4 + 4 + 2 + 4) + 64;
-  r = e->scratch(bytes);
+  QStage q{e, n};
+  r = q.reserve(4 + 4 + 4 + 2);
   if (r) return r;
-  char* b = (char*)e->qbuf;
-  u32* d_doc = (u32*)b;
-  u32* d_pos = d_doc + n;
-  u32* d_seq = d_pos + n;
-  u16* d_ag = (u16*)(d_seq + n);
-  HIPCHK(hipMemcpyAsync(d_doc, doc, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_pos, pos, n * 4, hipMemcpyHostToDevice, e->stream));
+  u32* d_doc = q.in(doc);
+  u32* d_pos = q.in(pos);
+  u32* d_seq = q.out(seq);
+  u16* d_ag = q.out(agent);
+  if (q.err) return q.err;
   r = crdt_pos_to_loc_dev_async(e, n, d_doc, d_pos, d_ag, d_seq);
-  if (r) return r;
-  HIPCHK(hipMemcpyAsync(agent, d_ag, n * 2, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(seq, d_seq, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return r ? r : q.finish();
 }
 
 int crdt_loc_to_pos(crdt_engine* e, uint64_t n, const uint32_t* doc, const uint16_t* agent, const uint32_t* seq, uint32_t* pos, uint8_t* deleted) {
@@ -2601,24 +2471,17 @@ int crdt_loc_to_pos(crdt_engine* e, uint64_t n, const uint32_t* doc, const uint1
   if (!n) return 0;
   int r = e->ensure_published();
   if (r) return r;
-  u64 bytes = n * (4 + 4 + 4 + 2 + 1) + 64;
-  r = e->scratch(bytes);
+  QStage q{e, n};
+  r = q.reserve(4 + 4 + 4 + 2 + 1);
   if (r) return r;
-  char* b = (char*)e->qbuf;
-  u32* d_doc = (u32*)b;
-  u32* d_seq = d_doc + n;
-  u32* d_pos = d_seq + n;
-  u16* d_ag = (u16*)(d_pos + n);
-  u8* d_del = (u8*)(d_ag + n);
-  HIPCHK(hipMemcpyAsync(d_doc, doc, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_seq, seq, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_ag, agent, n * 2, hipMemcpyHostToDevice, e->stream));
+  u32* d_doc = q.in(doc);
+  u32* d_seq = q.in(seq);
+  u32* d_pos = q.out(pos);
+  u16* d_ag = q.in(agent);
+  u8* d_del = q.out(deleted);
+  if (q.err) return q.err;
   r = crdt_loc_to_pos_dev_async(e, n, d_doc, d_ag, d_seq, d_pos, d_del);
-  if (r) return r;
-  HIPCHK(hipMemcpyAsync(pos, d_pos, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(deleted, d_del, n, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return r ? r : q.finish();
 }
 
 int crdt_doc_len(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* len) {
@@ -2757,14 +2620,11 @@ int crdt_device_bytes(uint64_t* current, uint64_t* peak, int reset_peak) {
 uint64_t crdt_mem_bytes(const crdt_engine* e) {
   if (!e) return 0;
   return e->pools.bytes + e->rec_cap * sizeof(Rec) + e->content_cap * 4 + e->text_cap * 4 + e->canon_alloc * 28 +
-         e->pub_alloc * 4 + e->probe_cap * 16 + e->diff_bm_cap * 4 + e->diff_pat_cap * sizeof(Patch) + e->diff_ins_cap * 8 +
-         e->diff_n_cap * (4 + 4 + 8 + sizeof(DiffRes)) +
-         (e->co_bm_cap + e->co_rk_cap + e->co_opos_cap + 2 * e->co_out_cap) * 4 +
-         e->co_n_cap * (4 + 4 + 8 + 8 + sizeof(CoRes)) +
-         e->blame_run_cap * sizeof(BlameRun) + e->blame_n_cap * (4 + sizeof(BlameRes)) +
-         e->enc_unit_cap + e->enc_sp_cap * 4 + e->enc_n_cap * (4 + 8 + sizeof(EncRes)) +
-         e->ln_tab_cap * sizeof(LineStart) + e->ln_n_cap * sizeof(LnRes) +
-         e->fd_tab_cap * sizeof(Match) + e->fd_n_cap * sizeof(FdRes) + (e->fd_pat ? FD_PAT_W * 4u : 0u) +
+         e->pub_alloc * 4 + e->probe_cap * 16 +
+         buf_bytes(e->diff.res, e->diff_docs, e->diff_since, e->diff_bm_base, e->diff_bm, e->diff_pat, e->diff_io, e->diff_it) +
+         buf_bytes(e->co.res, e->co_docs, e->co_ver, e->co_bm_base, e->co_sp_base, e->co_bm, e->co_rk, e->co_opos, e->co_ord, e->co_text) +
+         buf_bytes(e->blame.res, e->blame_docs, e->blame_runs, e->enc.res, e->enc_docs, e->enc_sp_base, e->enc_samples, e->enc_units) +
+         buf_bytes(e->ln.res, e->ln_tab, e->fd.res, e->fd_tab, e->fd_pat) +
          e->n_docs * (sizeof(DocState) + sizeof(DocSeg) + 4 + 4 + 8);
 }
 
@@ -2843,20 +2703,16 @@ int crdt_doc_version(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* 
 int crdt_diff_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* since) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e) || (n_docs && (!docs || !since)) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
-  g_alloc_oom = false;
-  int r = e->diff(n_docs, docs, since);
-  // (no relayout is involved: an allocation that fails leaves the engine as it was, without a diff result)
-  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
-  return r;
+  return oom_as_nomem([&] { return e->run_diff(n_docs, docs, since); });
 }
 
 int crdt_diff_counts(crdt_engine* e, uint32_t* n_patches, uint32_t* n_ins) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e)) return CRDT_E_ARG;
-  int r = e->diff_finish();
+  int r = e->diff.finish();
   if (r) return r;
-  for (u64 i = 0; i < e->diff_n; i++) {
-    const DiffRes& x = e->diff_res_h[i];
+  for (u64 i = 0; i < e->diff.n; i++) {
+    const DiffRes& x = e->diff.res_h[i];
     bool bad = (x.flags & DIFF_BAD) != 0;
     if (n_patches) n_patches[i] = bad ? INVALID : x.n_pat;
     if (n_ins) n_ins[i] = bad ? INVALID : x.n_ins;
@@ -2867,10 +2723,10 @@ int crdt_diff_counts(crdt_engine* e, uint32_t* n_patches, uint32_t* n_ins) {
 int crdt_diff_read(crdt_engine* e, uint64_t i, crdt_patch* patches, uint32_t* ins_order, uint32_t* ins_text) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e)) return CRDT_E_ARG;
-  int r = e->diff_finish();
+  int r = e->diff.finish();
   if (r) return r;
-  if (i >= e->diff_n) return CRDT_E_ARG;
-  const DiffRes& x = e->diff_res_h[i];
+  if (i >= e->diff.n) return CRDT_E_ARG;
+  const DiffRes& x = e->diff.res_h[i];
   if (x.flags & DIFF_BAD) {
     g_last_error = "diff: since above the document's version, or a poisoned document";
     return CRDT_E_ARG;
@@ -2879,45 +2735,33 @@ int crdt_diff_read(crdt_engine* e, uint64_t i, crdt_patch* patches, uint32_t* in
     g_last_error = "diff: the document has no content (or too short a stream) for ins_text";
     return CRDT_E_ARG;
   }
-  if (patches && x.n_pat) HIPCHK(hipMemcpy(patches, e->diff_pat + x.poff, (u64)x.n_pat * sizeof(Patch), hipMemcpyDeviceToHost));
-  if (ins_order && x.n_ins) HIPCHK(hipMemcpy(ins_order, e->diff_io + x.ioff, (u64)x.n_ins * 4, hipMemcpyDeviceToHost));
-  if (ins_text && x.n_ins) HIPCHK(hipMemcpy(ins_text, e->diff_it + x.ioff, (u64)x.n_ins * 4, hipMemcpyDeviceToHost));
+  if (patches && x.n_pat) HIPCHK(hipMemcpy(patches, e->diff_pat.p + x.poff, (u64)x.n_pat * sizeof(Patch), hipMemcpyDeviceToHost));
+  if (ins_order && x.n_ins) HIPCHK(hipMemcpy(ins_order, e->diff_io.p + x.ioff, (u64)x.n_ins * 4, hipMemcpyDeviceToHost));
+  if (ins_text && x.n_ins) HIPCHK(hipMemcpy(ins_text, e->diff_it.p + x.ioff, (u64)x.n_ins * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
-int crdt_last_diff_ms(crdt_engine* e, double* ms) {
-  if (!e || !ms) return CRDT_E_ARG;
-  if (e->diff_valid && !e->diff_pulled) {
-    int r = e->diff_finish();
-    if (r) return r;
-  }
-  *ms = e->last_diff_ms;
-  return 0;
-}
+int crdt_last_diff_ms(crdt_engine* e, double* ms) { return job_ms(e, &crdt_engine::diff, ms); }
 
 int crdt_checkout_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* version) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e) || (n_docs && (!docs || !version)) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
-  g_alloc_oom = false;
-  int r = e->checkout(n_docs, docs, version);
-  // (no relayout is involved: an allocation that fails leaves the engine as it was, without a checkout)
-  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
-  return r;
+  return oom_as_nomem([&] { return e->run_checkout(n_docs, docs, version); });
 }
 
 int crdt_checkout_lens(crdt_engine* e, uint32_t* len) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e)) return CRDT_E_ARG;
-  int r = e->co_finish();
+  int r = e->co.finish();
   if (r) return r;
-  for (u64 i = 0; len && i < e->co_n; i++) len[i] = (e->co_res_h[i].flags & CO_BAD) ? INVALID : e->co_res_h[i].len;
+  for (u64 i = 0; len && i < e->co.n; i++) len[i] = (e->co.res_h[i].flags & CO_BAD) ? INVALID : e->co.res_h[i].len;
   return 0;
 }
 
 // result i of the last checkout, or nullptr (with the error text set) when the index has none
 static const CoRes* co_result(crdt_engine* e, uint64_t i) {
-  if (i >= e->co_n) return nullptr;
-  const CoRes& x = e->co_res_h[i];
+  if (i >= e->co.n) return nullptr;
+  const CoRes& x = e->co.res_h[i];
   if (x.flags & CO_BAD) {
     g_last_error = "checkout: version above the document's version, or a poisoned document";
     return nullptr;
@@ -2928,7 +2772,7 @@ static const CoRes* co_result(crdt_engine* e, uint64_t i) {
 int crdt_checkout_read(crdt_engine* e, uint64_t i, uint32_t* order, uint32_t* text) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e)) return CRDT_E_ARG;
-  int r = e->co_finish();
+  int r = e->co.finish();
   if (r) return r;
   const CoRes* x = co_result(e, i);
   if (!x) return CRDT_E_ARG;
@@ -2936,29 +2780,21 @@ int crdt_checkout_read(crdt_engine* e, uint64_t i, uint32_t* order, uint32_t* te
     g_last_error = "checkout: the document has no content (or too short a stream) for text";
     return CRDT_E_ARG;
   }
-  if (order && x->len) HIPCHK(hipMemcpy(order, e->co_ord + x->off, (u64)x->len * 4, hipMemcpyDeviceToHost));
-  if (text && x->len) HIPCHK(hipMemcpy(text, e->co_text + x->off, (u64)x->len * 4, hipMemcpyDeviceToHost));
+  if (order && x->len) HIPCHK(hipMemcpy(order, e->co_ord.p + x->off, (u64)x->len * 4, hipMemcpyDeviceToHost));
+  if (text && x->len) HIPCHK(hipMemcpy(text, e->co_text.p + x->off, (u64)x->len * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int crdt_checkout_digest(crdt_engine* e, uint64_t* per_index) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e)) return CRDT_E_ARG;
-  int r = e->co_finish();
+  int r = e->co.finish();
   if (r) return r;
-  for (u64 i = 0; per_index && i < e->co_n; i++) per_index[i] = (e->co_res_h[i].flags & CO_BAD) ? 0ull : e->co_res_h[i].digest;
+  for (u64 i = 0; per_index && i < e->co.n; i++) per_index[i] = (e->co.res_h[i].flags & CO_BAD) ? 0ull : e->co.res_h[i].digest;
   return 0;
 }
 
-int crdt_last_checkout_ms(crdt_engine* e, double* ms) {
-  if (!e || !ms) return CRDT_E_ARG;
-  if (e->co_valid && !e->co_pulled) {
-    int r = e->co_finish();
-    if (r) return r;
-  }
-  *ms = e->last_co_ms;
-  return 0;
-}
+int crdt_last_checkout_ms(crdt_engine* e, double* ms) { return job_ms(e, &crdt_engine::co, ms); }
 
 int crdt_blame_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, int mode) {
   if (poisoned(e)) return CRDT_E_NOMEM;
@@ -2967,67 +2803,51 @@ int crdt_blame_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, int 
     g_last_error = "blame: mode is CRDT_BLAME_AGENT or CRDT_BLAME_ID";
     return CRDT_E_ARG;
   }
-  g_alloc_oom = false;
-  int r = e->blame(n_docs, docs, (u32)mode);
-  // (no relayout is involved: an allocation that fails leaves the engine as it was, without a blame result)
-  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
-  return r;
+  return oom_as_nomem([&] { return e->run_blame(n_docs, docs, (u32)mode); });
 }
 
 int crdt_blame_counts(crdt_engine* e, uint32_t* n_runs) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e)) return CRDT_E_ARG;
-  int r = e->blame_finish();
+  int r = e->blame.finish();
   if (r) return r;
-  for (u64 i = 0; n_runs && i < e->blame_n; i++) n_runs[i] = (e->blame_res_h[i].flags & BLAME_BAD) ? INVALID : e->blame_res_h[i].n_runs;
+  for (u64 i = 0; n_runs && i < e->blame.n; i++) n_runs[i] = (e->blame.res_h[i].flags & BLAME_BAD) ? INVALID : e->blame.res_h[i].n_runs;
   return 0;
 }
 
 int crdt_blame_read(crdt_engine* e, uint64_t i, crdt_blame_run* runs) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e)) return CRDT_E_ARG;
-  int r = e->blame_finish();
+  int r = e->blame.finish();
   if (r) return r;
-  if (i >= e->blame_n) return CRDT_E_ARG;
-  const BlameRes& x = e->blame_res_h[i];
+  if (i >= e->blame.n) return CRDT_E_ARG;
+  const BlameRes& x = e->blame.res_h[i];
   if (x.flags & BLAME_BAD) {
     g_last_error = "blame: a poisoned document";
     return CRDT_E_ARG;
   }
-  if (runs && x.n_runs) HIPCHK(hipMemcpy(runs, e->blame_runs + x.off, (u64)x.n_runs * sizeof(BlameRun), hipMemcpyDeviceToHost));
+  if (runs && x.n_runs) HIPCHK(hipMemcpy(runs, e->blame_runs.p + x.off, (u64)x.n_runs * sizeof(BlameRun), hipMemcpyDeviceToHost));
   return 0;
 }
 
-int crdt_last_blame_ms(crdt_engine* e, double* ms) {
-  if (!e || !ms) return CRDT_E_ARG;
-  if (e->blame_valid && !e->blame_pulled) {
-    int r = e->blame_finish();
-    if (r) return r;
-  }
-  *ms = e->last_blame_ms;
-  return 0;
-}
+int crdt_last_blame_ms(crdt_engine* e, double* ms) { return job_ms(e, &crdt_engine::blame, ms); }
 
 int crdt_encode_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, int enc) {
   if (poisoned(e)) return CRDT_E_NOMEM;
-  if (e) e->ln_valid = e->ln_pulled = false;  // (a later encode call, successful or not, drops the line index)
-  if (e) e->fd_valid = e->fd_pulled = false;  // (... and the find result)
+  if (e) e->ln.drop();  // (a later encode call, successful or not, drops the line index)
+  if (e) e->fd.drop();  // (... and the find result)
   if (!valid(e) || (n_docs && !docs) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
   if (enc != CRDT_ENC_UTF8 && enc != CRDT_ENC_UTF16) {
     g_last_error = "encode: enc is CRDT_ENC_UTF8 or CRDT_ENC_UTF16";
     return CRDT_E_ARG;
   }
-  g_alloc_oom = false;
-  int r = e->encode(n_docs, docs, (u32)enc);
-  // (no relayout is involved: an allocation that fails leaves the engine as it was, without an encode result)
-  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
-  return r;
+  return oom_as_nomem([&] { return e->run_encode(n_docs, docs, (u32)enc); });
 }
 
 // result i of the last encode, or nullptr (with the error text set) when the index has none
 static const EncRes* enc_result(crdt_engine* e, uint64_t i) {
-  if (i >= e->enc_n) return nullptr;
-  const EncRes& x = e->enc_res_h[i];
+  if (i >= e->enc.n) return nullptr;
+  const EncRes& x = e->enc.res_h[i];
   if (x.units == INVALID) {
     g_last_error = "encode: a poisoned document, or one without content (or with too short a stream)";
     return nullptr;
@@ -3038,11 +2858,11 @@ static const EncRes* enc_result(crdt_engine* e, uint64_t i) {
 int crdt_encode_lens(crdt_engine* e, uint32_t* units, uint32_t* chars) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e)) return CRDT_E_ARG;
-  int r = e->enc_finish();
+  int r = e->enc.finish();
   if (r) return r;
-  for (u64 i = 0; i < e->enc_n; i++) {
-    if (units) units[i] = e->enc_res_h[i].units;
-    if (chars) chars[i] = e->enc_res_h[i].chars;
+  for (u64 i = 0; i < e->enc.n; i++) {
+    if (units) units[i] = e->enc.res_h[i].units;
+    if (chars) chars[i] = e->enc.res_h[i].chars;
   }
   return 0;
 }
@@ -3050,27 +2870,19 @@ int crdt_encode_lens(crdt_engine* e, uint32_t* units, uint32_t* chars) {
 int crdt_encode_read(crdt_engine* e, uint64_t i, void* out, uint64_t cap_units) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e)) return CRDT_E_ARG;
-  int r = e->enc_finish();
+  int r = e->enc.finish();
   if (r) return r;
   const EncRes* x = enc_result(e, i);
   if (!x || cap_units < x->units || (x->units && !out)) return CRDT_E_ARG;
   u64 usz = e->enc_mode == ENC_UTF8 ? 1u : 2u;
-  if (x->units) HIPCHK(hipMemcpy(out, e->enc_units + x->off * usz, (u64)x->units * usz, hipMemcpyDeviceToHost));
+  if (x->units) HIPCHK(hipMemcpy(out, e->enc_units.p + x->off * usz, (u64)x->units * usz, hipMemcpyDeviceToHost));
   return 0;
 }
 
-int crdt_last_encode_ms(crdt_engine* e, double* ms) {
-  if (!e || !ms) return CRDT_E_ARG;
-  if (e->enc_valid && !e->enc_pulled) {
-    int r = e->enc_finish();
-    if (r) return r;
-  }
-  *ms = e->last_enc_ms;
-  return 0;
-}
+int crdt_last_encode_ms(crdt_engine* e, double* ms) { return job_ms(e, &crdt_engine::enc, ms); }
 
 static int enc_query_ok(crdt_engine* e) {
-  if (!e->enc_valid) {
+  if (!e->enc.valid) {
     g_last_error = "encode: no encode result";
     return CRDT_E_ARG;
   }
@@ -3085,9 +2897,9 @@ int crdt_pos_to_units_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx,
   if (!n) return 0;
   u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
   if (e->enc_mode == ENC_UTF8)
-    hipLaunchKernelGGL(k_pos_to_units<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc_n, n, idx, pos, unit);
+    hipLaunchKernelGGL(k_pos_to_units<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc.n, n, idx, pos, unit);
   else
-    hipLaunchKernelGGL(k_pos_to_units<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc_n, n, idx, pos, unit);
+    hipLaunchKernelGGL(k_pos_to_units<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc.n, n, idx, pos, unit);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3101,9 +2913,9 @@ int crdt_units_to_pos_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx,
   if (!n) return 0;
   u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
   if (e->enc_mode == ENC_UTF8)
-    hipLaunchKernelGGL(k_units_to_pos<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc_n, n, idx, unit, pos, mid);
+    hipLaunchKernelGGL(k_units_to_pos<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc.n, n, idx, unit, pos, mid);
   else
-    hipLaunchKernelGGL(k_units_to_pos<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc_n, n, idx, unit, pos, mid);
+    hipLaunchKernelGGL(k_units_to_pos<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), (u32)e->enc.n, n, idx, unit, pos, mid);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3112,7 +2924,7 @@ int crdt_units_to_pos_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx,
 static int enc_idx_ok(crdt_engine* e, uint64_t n, const uint32_t* idx) {
   int r = enc_query_ok(e);
   if (r) return r;
-  r = e->enc_finish();
+  r = e->enc.finish();
   if (r) return r;
   for (uint64_t q = 0; q < n; q++)
     if (!enc_result(e, idx[q])) return CRDT_E_ARG;
@@ -3124,18 +2936,15 @@ int crdt_pos_to_units(crdt_engine* e, uint64_t n, const uint32_t* idx, const uin
   if (!valid(e) || (n && (!idx || !pos || !unit))) return CRDT_E_ARG;
   int r = enc_idx_ok(e, n, idx);
   if (r || !n) return r;
-  r = e->scratch(n * (4 + 4 + 4) + 64);
+  QStage q{e, n};
+  r = q.reserve(4 + 4 + 4);
   if (r) return r;
-  u32* d_idx = (u32*)e->qbuf;
-  u32* d_pos = d_idx + n;
-  u32* d_unit = d_pos + n;
-  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_pos, pos, n * 4, hipMemcpyHostToDevice, e->stream));
+  u32* d_idx = q.in(idx);
+  u32* d_pos = q.in(pos);
+  u32* d_unit = q.out(unit);
+  if (q.err) return q.err;
   r = crdt_pos_to_units_dev_async(e, n, d_idx, d_pos, d_unit);
-  if (r) return r;
-  HIPCHK(hipMemcpyAsync(unit, d_unit, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return r ? r : q.finish();
 }
 
 int crdt_units_to_pos(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* unit, uint32_t* pos, uint8_t* mid) {
@@ -3143,20 +2952,16 @@ int crdt_units_to_pos(crdt_engine* e, uint64_t n, const uint32_t* idx, const uin
   if (!valid(e) || (n && (!idx || !unit || !pos))) return CRDT_E_ARG;
   int r = enc_idx_ok(e, n, idx);
   if (r || !n) return r;
-  r = e->scratch(n * (4 + 4 + 4 + 1) + 64);
+  QStage q{e, n};
+  r = q.reserve(4 + 4 + 4 + 1);
   if (r) return r;
-  u32* d_idx = (u32*)e->qbuf;
-  u32* d_unit = d_idx + n;
-  u32* d_pos = d_unit + n;
-  u8* d_mid = (u8*)(d_pos + n);
-  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_unit, unit, n * 4, hipMemcpyHostToDevice, e->stream));
+  u32* d_idx = q.in(idx);
+  u32* d_unit = q.in(unit);
+  u32* d_pos = q.out(pos);
+  u8* d_mid = q.out(mid);
+  if (q.err) return q.err;
   r = crdt_units_to_pos_dev_async(e, n, d_idx, d_unit, d_pos, mid ? d_mid : nullptr);
-  if (r) return r;
-  HIPCHK(hipMemcpyAsync(pos, d_pos, n * 4, hipMemcpyDeviceToHost, e->stream));
-  if (mid) HIPCHK(hipMemcpyAsync(mid, d_mid, n, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return r ? r : q.finish();
 }
 
 int crdt_lines_async(crdt_engine* e, int eol) {
@@ -3168,15 +2973,11 @@ int crdt_lines_async(crdt_engine* e, int eol) {
   }
   int r = enc_query_ok(e);
   if (r) return r;
-  g_alloc_oom = false;
-  r = e->lines((u32)eol);
-  // (an allocation that fails leaves the engine as it was, with its encode result and without a line index)
-  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
-  return r;
+  return oom_as_nomem([&] { return e->run_lines((u32)eol); });
 }
 
 static int ln_query_ok(crdt_engine* e) {
-  if (!e->ln_valid) {
+  if (!e->ln.valid) {
     g_last_error = "lines: no line index (of the current encode result)";
     return CRDT_E_ARG;
   }
@@ -3191,8 +2992,8 @@ static int col_kind_ok(int col_kind) {
 }
 // line count i of the last line index, or nullptr (with the error text set) when the index has none
 static const LnRes* ln_result(crdt_engine* e, uint64_t i) {
-  if (i >= e->enc_n) return nullptr;
-  const LnRes& x = e->ln_res_h[i];
+  if (i >= e->enc.n) return nullptr;
+  const LnRes& x = e->ln.res_h[i];
   if (x.n_lines == INVALID) {
     g_last_error = "lines: the encode has no result for this index";
     return nullptr;
@@ -3205,10 +3006,10 @@ int crdt_line_counts(crdt_engine* e, uint32_t* n_lines) {
   if (!valid(e)) return CRDT_E_ARG;
   int r = ln_query_ok(e);
   if (r) return r;
-  r = e->ln_finish();
+  r = e->ln.finish();
   if (r) return r;
-  for (u64 i = 0; i < e->enc_n; i++)
-    if (n_lines) n_lines[i] = e->ln_res_h[i].n_lines;
+  for (u64 i = 0; i < e->enc.n; i++)
+    if (n_lines) n_lines[i] = e->ln.res_h[i].n_lines;
   return 0;
 }
 
@@ -3217,23 +3018,15 @@ int crdt_lines_read(crdt_engine* e, uint64_t i, crdt_line_start* starts) {
   if (!valid(e)) return CRDT_E_ARG;
   int r = ln_query_ok(e);
   if (r) return r;
-  r = e->ln_finish();
+  r = e->ln.finish();
   if (r) return r;
   const LnRes* x = ln_result(e, i);
   if (!x || !starts) return CRDT_E_ARG;
-  HIPCHK(hipMemcpy(starts, e->ln_tab + x->off, (u64)x->n_lines * sizeof(LineStart), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(starts, e->ln_tab.p + x->off, (u64)x->n_lines * sizeof(LineStart), hipMemcpyDeviceToHost));
   return 0;
 }
 
-int crdt_last_lines_ms(crdt_engine* e, double* ms) {
-  if (!e || !ms) return CRDT_E_ARG;
-  if (e->ln_valid && !e->ln_pulled) {
-    int r = e->ln_finish();
-    if (r) return r;
-  }
-  *ms = e->last_ln_ms;
-  return 0;
-}
+int crdt_last_lines_ms(crdt_engine* e, double* ms) { return job_ms(e, &crdt_engine::ln, ms); }
 
 int crdt_pos_to_linecol_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, int col_kind,
                                   uint32_t* line, uint32_t* col) {
@@ -3246,10 +3039,10 @@ int crdt_pos_to_linecol_dev_async(crdt_engine* e, uint64_t n, const uint32_t* id
   if (!n) return 0;
   u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
   if (e->enc_mode == ENC_UTF8)
-    hipLaunchKernelGGL(k_pos_to_linecol<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc_n, n,
+    hipLaunchKernelGGL(k_pos_to_linecol<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc.n, n,
                        idx, pos, (u32)col_kind, line, col);
   else
-    hipLaunchKernelGGL(k_pos_to_linecol<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc_n, n,
+    hipLaunchKernelGGL(k_pos_to_linecol<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc.n, n,
                        idx, pos, (u32)col_kind, line, col);
   HIPCHK(hipGetLastError());
   return 0;
@@ -3266,10 +3059,10 @@ int crdt_linecol_to_pos_dev_async(crdt_engine* e, uint64_t n, const uint32_t* id
   if (!n) return 0;
   u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
   if (e->enc_mode == ENC_UTF8)
-    hipLaunchKernelGGL(k_linecol_to_pos<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc_n, n,
+    hipLaunchKernelGGL(k_linecol_to_pos<ENC_UTF8>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc.n, n,
                        idx, line, col, (u32)col_kind, pos, mid);
   else
-    hipLaunchKernelGGL(k_linecol_to_pos<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc_n, n,
+    hipLaunchKernelGGL(k_linecol_to_pos<ENC_UTF16>, dim3(blocks), dim3(256), 0, e->stream, e->enc_view(), e->ln_view(), (u32)e->enc.n, n,
                        idx, line, col, (u32)col_kind, pos, mid);
   HIPCHK(hipGetLastError());
   return 0;
@@ -3281,7 +3074,7 @@ static int ln_idx_ok(crdt_engine* e, uint64_t n, const uint32_t* idx, int col_ki
   if (r) return r;
   r = ln_query_ok(e);
   if (r) return r;
-  r = e->ln_finish();
+  r = e->ln.finish();
   if (r) return r;
   for (uint64_t q = 0; q < n; q++)
     if (!ln_result(e, idx[q])) return CRDT_E_ARG;
@@ -3294,20 +3087,16 @@ int crdt_pos_to_linecol(crdt_engine* e, uint64_t n, const uint32_t* idx, const u
   if (!valid(e) || (n && (!idx || !pos || !line || !col))) return CRDT_E_ARG;
   int r = ln_idx_ok(e, n, idx, col_kind);
   if (r || !n) return r;
-  r = e->scratch(n * (4 + 4 + 4 + 4) + 64);
+  QStage q{e, n};
+  r = q.reserve(4 + 4 + 4 + 4);
   if (r) return r;
-  u32* d_idx = (u32*)e->qbuf;
-  u32* d_pos = d_idx + n;
-  u32* d_line = d_pos + n;
-  u32* d_col = d_line + n;
-  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_pos, pos, n * 4, hipMemcpyHostToDevice, e->stream));
+  u32* d_idx = q.in(idx);
+  u32* d_pos = q.in(pos);
+  u32* d_line = q.out(line);
+  u32* d_col = q.out(col);
+  if (q.err) return q.err;
   r = crdt_pos_to_linecol_dev_async(e, n, d_idx, d_pos, col_kind, d_line, d_col);
-  if (r) return r;
-  HIPCHK(hipMemcpyAsync(line, d_line, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(col, d_col, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return r ? r : q.finish();
 }
 
 int crdt_linecol_to_pos(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* line, const uint32_t* col,
@@ -3316,22 +3105,17 @@ int crdt_linecol_to_pos(crdt_engine* e, uint64_t n, const uint32_t* idx, const u
   if (!valid(e) || (n && (!idx || !line || !col || !pos))) return CRDT_E_ARG;
   int r = ln_idx_ok(e, n, idx, col_kind);
   if (r || !n) return r;
-  r = e->scratch(n * (4 + 4 + 4 + 4 + 1) + 64);
+  QStage q{e, n};
+  r = q.reserve(4 + 4 + 4 + 4 + 1);
   if (r) return r;
-  u32* d_idx = (u32*)e->qbuf;
-  u32* d_line = d_idx + n;
-  u32* d_col = d_line + n;
-  u32* d_pos = d_col + n;
-  u8* d_mid = (u8*)(d_pos + n);
-  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_line, line, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_col, col, n * 4, hipMemcpyHostToDevice, e->stream));
+  u32* d_idx = q.in(idx);
+  u32* d_line = q.in(line);
+  u32* d_col = q.in(col);
+  u32* d_pos = q.out(pos);
+  u8* d_mid = q.out(mid);
+  if (q.err) return q.err;
   r = crdt_linecol_to_pos_dev_async(e, n, d_idx, d_line, d_col, col_kind, d_pos, mid ? d_mid : nullptr);
-  if (r) return r;
-  HIPCHK(hipMemcpyAsync(pos, d_pos, n * 4, hipMemcpyDeviceToHost, e->stream));
-  if (mid) HIPCHK(hipMemcpyAsync(mid, d_mid, n, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return r ? r : q.finish();
 }
 
 int crdt_find_async(crdt_engine* e, const uint32_t* pattern, uint32_t n_chars, int flags) {
@@ -3347,15 +3131,11 @@ int crdt_find_async(crdt_engine* e, const uint32_t* pattern, uint32_t n_chars, i
   }
   int r = enc_query_ok(e);
   if (r) return r;
-  g_alloc_oom = false;
-  r = e->find(pattern, n_chars, (u32)flags);
-  // (an allocation that fails leaves the engine as it was, with its encode result and its line index and without a find result)
-  if (r == CRDT_E_DEVICE && g_alloc_oom) r = CRDT_E_NOMEM;
-  return r;
+  return oom_as_nomem([&] { return e->run_find(pattern, n_chars, (u32)flags); });
 }
 
 static int fd_query_ok(crdt_engine* e) {
-  if (!e->fd_valid) {
+  if (!e->fd.valid) {
     g_last_error = "find: no find result (of the current encode result)";
     return CRDT_E_ARG;
   }
@@ -3370,8 +3150,8 @@ static int seek_dir_ok(int dir) {
 }
 // match count i of the last find, or nullptr (with the error text set) when the index has none
 static const FdRes* fd_result(crdt_engine* e, uint64_t i) {
-  if (i >= e->enc_n) return nullptr;
-  const FdRes& x = e->fd_res_h[i];
+  if (i >= e->enc.n) return nullptr;
+  const FdRes& x = e->fd.res_h[i];
   if (x.n_matches == INVALID) {
     g_last_error = "find: the encode has no result for this index";
     return nullptr;
@@ -3384,10 +3164,10 @@ int crdt_find_counts(crdt_engine* e, uint32_t* n_matches) {
   if (!valid(e)) return CRDT_E_ARG;
   int r = fd_query_ok(e);
   if (r) return r;
-  r = e->fd_finish();
+  r = e->fd.finish();
   if (r) return r;
-  for (u64 i = 0; i < e->enc_n; i++)
-    if (n_matches) n_matches[i] = e->fd_res_h[i].n_matches;
+  for (u64 i = 0; i < e->enc.n; i++)
+    if (n_matches) n_matches[i] = e->fd.res_h[i].n_matches;
   return 0;
 }
 
@@ -3396,23 +3176,15 @@ int crdt_find_read(crdt_engine* e, uint64_t i, crdt_match* matches) {
   if (!valid(e)) return CRDT_E_ARG;
   int r = fd_query_ok(e);
   if (r) return r;
-  r = e->fd_finish();
+  r = e->fd.finish();
   if (r) return r;
   const FdRes* x = fd_result(e, i);
   if (!x || (x->n_matches && !matches)) return CRDT_E_ARG;
-  if (x->n_matches) HIPCHK(hipMemcpy(matches, e->fd_tab + x->off, (u64)x->n_matches * sizeof(Match), hipMemcpyDeviceToHost));
+  if (x->n_matches) HIPCHK(hipMemcpy(matches, e->fd_tab.p + x->off, (u64)x->n_matches * sizeof(Match), hipMemcpyDeviceToHost));
   return 0;
 }
 
-int crdt_last_find_ms(crdt_engine* e, double* ms) {
-  if (!e || !ms) return CRDT_E_ARG;
-  if (e->fd_valid && !e->fd_pulled) {
-    int r = e->fd_finish();
-    if (r) return r;
-  }
-  *ms = e->last_fd_ms;
-  return 0;
-}
+int crdt_last_find_ms(crdt_engine* e, double* ms) { return job_ms(e, &crdt_engine::fd, ms); }
 
 int crdt_find_seek_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* pos, int dir, uint32_t* k) {
   if (poisoned(e)) return CRDT_E_NOMEM;
@@ -3423,7 +3195,7 @@ int crdt_find_seek_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, co
   if (r) return r;
   if (!n) return 0;
   u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
-  hipLaunchKernelGGL(k_find_seek, dim3(blocks), dim3(256), 0, e->stream, e->fd_view(), (u32)e->enc_n, n, idx, pos, (u32)dir, k);
+  hipLaunchKernelGGL(k_find_seek, dim3(blocks), dim3(256), 0, e->stream, e->fd_view(), (u32)e->enc.n, n, idx, pos, (u32)dir, k);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3435,24 +3207,21 @@ int crdt_find_seek(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32
   if (r) return r;
   r = fd_query_ok(e);
   if (r) return r;
-  r = e->fd_finish();
+  r = e->fd.finish();
   if (r) return r;
   // the host form names only indexes that have a result (checked before anything is written)
   for (uint64_t q = 0; q < n; q++)
     if (!fd_result(e, idx[q])) return CRDT_E_ARG;
   if (!n) return 0;
-  r = e->scratch(n * (4 + 4 + 4) + 64);
+  QStage q{e, n};
+  r = q.reserve(4 + 4 + 4);
   if (r) return r;
-  u32* d_idx = (u32*)e->qbuf;
-  u32* d_pos = d_idx + n;
-  u32* d_k = d_pos + n;
-  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_pos, pos, n * 4, hipMemcpyHostToDevice, e->stream));
+  u32* d_idx = q.in(idx);
+  u32* d_pos = q.in(pos);
+  u32* d_k = q.out(k);
+  if (q.err) return q.err;
   r = crdt_find_seek_dev_async(e, n, d_idx, d_pos, dir, d_k);
-  if (r) return r;
-  HIPCHK(hipMemcpyAsync(k, d_k, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return r ? r : q.finish();
 }
 
 static int co_query_ok(crdt_engine* e) {
@@ -3471,7 +3240,7 @@ int crdt_pos_to_loc_at_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx
   if (r) return r;
   if (!n) return 0;
   u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
-  hipLaunchKernelGGL(k_pos_to_loc_at, dim3(blocks), dim3(256), 0, e->stream, e->pools_view(e->pools), e->co_view(), (u32)e->co_n, n,
+  hipLaunchKernelGGL(k_pos_to_loc_at, dim3(blocks), dim3(256), 0, e->stream, e->pools_view(e->pools), e->co_view(), (u32)e->co.n, n,
                      idx, pos, agent, seq);
   HIPCHK(hipGetLastError());
   return 0;
@@ -3486,7 +3255,7 @@ int crdt_loc_to_pos_at_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx
   if (!n) return 0;
   u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
   hipLaunchKernelGGL(k_loc_to_pos_at, dim3(blocks), dim3(256), 0, e->stream, e->pools_view(e->pools), e->pub_view(), e->co_view(),
-                     (u32)e->co_n, n, idx, agent, seq, pos, deleted);
+                     (u32)e->co.n, n, idx, agent, seq, pos, deleted);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3495,7 +3264,7 @@ int crdt_loc_to_pos_at_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx
 static int co_idx_ok(crdt_engine* e, uint64_t n, const uint32_t* idx) {
   int r = co_query_ok(e);
   if (r) return r;
-  r = e->co_finish();
+  r = e->co.finish();
   if (r) return r;
   for (uint64_t q = 0; q < n; q++)
     if (!co_result(e, idx[q])) return CRDT_E_ARG;
@@ -3507,20 +3276,16 @@ int crdt_pos_to_loc_at(crdt_engine* e, uint64_t n, const uint32_t* idx, const ui
   if (!valid(e) || (n && (!idx || !pos || !agent || !seq))) return CRDT_E_ARG;
   int r = co_idx_ok(e, n, idx);
   if (r || !n) return r;
-  r = e->scratch(n * (4 + 4 + 2 + 4) + 64);
+  QStage q{e, n};
+  r = q.reserve(4 + 4 + 4 + 2);
   if (r) return r;
-  u32* d_idx = (u32*)e->qbuf;
-  u32* d_pos = d_idx + n;
-  u32* d_seq = d_pos + n;
-  u16* d_ag = (u16*)(d_seq + n);
-  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_pos, pos, n * 4, hipMemcpyHostToDevice, e->stream));
+  u32* d_idx = q.in(idx);
+  u32* d_pos = q.in(pos);
+  u32* d_seq = q.out(seq);
+  u16* d_ag = q.out(agent);
+  if (q.err) return q.err;
   r = crdt_pos_to_loc_at_dev_async(e, n, d_idx, d_pos, d_ag, d_seq);
-  if (r) return r;
-  HIPCHK(hipMemcpyAsync(agent, d_ag, n * 2, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(seq, d_seq, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return r ? r : q.finish();
 }
 
 int crdt_loc_to_pos_at(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint16_t* agent, const uint32_t* seq, uint32_t* pos,
@@ -3529,22 +3294,17 @@ int crdt_loc_to_pos_at(crdt_engine* e, uint64_t n, const uint32_t* idx, const ui
   if (!valid(e) || (n && (!idx || !agent || !seq || !pos || !deleted))) return CRDT_E_ARG;
   int r = co_idx_ok(e, n, idx);
   if (r || !n) return r;
-  r = e->scratch(n * (4 + 4 + 4 + 2 + 1) + 64);
+  QStage q{e, n};
+  r = q.reserve(4 + 4 + 4 + 2 + 1);
   if (r) return r;
-  u32* d_idx = (u32*)e->qbuf;
-  u32* d_seq = d_idx + n;
-  u32* d_pos = d_seq + n;
-  u16* d_ag = (u16*)(d_pos + n);
-  u8* d_del = (u8*)(d_ag + n);
-  HIPCHK(hipMemcpyAsync(d_idx, idx, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_seq, seq, n * 4, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_ag, agent, n * 2, hipMemcpyHostToDevice, e->stream));
+  u32* d_idx = q.in(idx);
+  u32* d_seq = q.in(seq);
+  u32* d_pos = q.out(pos);
+  u16* d_ag = q.in(agent);
+  u8* d_del = q.out(deleted);
+  if (q.err) return q.err;
   r = crdt_loc_to_pos_at_dev_async(e, n, d_idx, d_ag, d_seq, d_pos, d_del);
-  if (r) return r;
-  HIPCHK(hipMemcpyAsync(pos, d_pos, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(deleted, d_del, n, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return r ? r : q.finish();
 }
 
 const char* crdt_last_error(void) { return g_last_error.c_str(); }

@@ -54,7 +54,7 @@ struct Match {
 struct FdRes {
   u32 n_matches;  // INVALID: no result for this index
   u32 pad_;
-  u64 off;        // first entry of this index in the table (k_find_scan)
+  u64 off;        // first entry of this index in the table (k_result_scan)
 };
 struct FdIO {
   FdRes* res;   // [i]
@@ -188,35 +188,11 @@ __global__ __launch_bounds__(LN_T) void k_find_count(EncIO E, FdIO F, FdPat Pt, 
   if (tid == 0) F.res[i] = FdRes{s_c[0] + s_c[1] + s_c[2] + s_c[3], 0u, 0ull};
 }
 
-// Exclusive scan of the indexes' match counts into their table offsets (k_ln_scan's shape);
-// *total = matches of all indexes.
-__global__ __launch_bounds__(DIFF_SCAN_T) void k_find_scan(FdRes* res, u32 n, u64* total) {
-  __shared__ u64 s_a[DIFF_SCAN_T];
-  u32 t = threadIdx.x;
-  u32 per = (n + DIFF_SCAN_T - 1u) / DIFF_SCAN_T;
-  u64 lo = min((u64)t * per, (u64)n), hi = min(lo + per, (u64)n);
-  u64 a = 0;
-  for (u64 k = lo; k < hi; k++) a += res[k].n_matches == INVALID ? 0ull : (u64)res[k].n_matches;
-  s_a[t] = a;
-  __syncthreads();
-  if (t == 0) {
-    a = 0;
-    for (u32 x = 0; x < DIFF_SCAN_T; x++) {
-      u64 p = s_a[x];
-      s_a[x] = a;
-      a += p;
-    }
-    *total = a;
-  }
-  __syncthreads();
-  a = s_a[t];
-  for (u64 k = lo; k < hi; k++) {
-    res[k].off = a;
-    a += res[k].n_matches == INVALID ? 0ull : (u64)res[k].n_matches;
-  }
-}
+// k_result_scan's view of an FdRes: its matches (an index without a result counts as 0)
+__device__ __forceinline__ void scan_counts(const FdRes& r, u64* c) { c[0] = r.n_matches == INVALID ? 0ull : (u64)r.n_matches; }
+__device__ __forceinline__ void scan_store(FdRes& r, const u64* off) { r.off = off[0]; }
 
-// Second sweep, after k_find_scan: the same passes, rows and windows.  Two running counts are
+// Second sweep, after k_result_scan: the same passes, rows and windows.  Two running counts are
 // carried from pass to pass in registers, as k_ln_write carries its: the matches so far (the rank
 // in the table) and the char starts so far (the char position).  A dword has at most 4 of each and
 // a pass at most 4,096, so both ride one wave scan per row as a packed pair (matches in the low,

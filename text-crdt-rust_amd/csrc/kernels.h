@@ -7,12 +7,12 @@
 //   k_pub_index the order->span index of k_publish's documents, built in LDS (block per document)
 //   k_pos_to_loc / k_loc_to_pos   batched lookups on the published index (thread per query)
 //   k_materialize  document text from the published index + content streams (block per document)
-//   k_diff_mark / k_diff / k_diff_scan  per-document text patches from a past version to now, from
+//   k_diff_mark / k_diff / k_result_scan  per-document text patches from a past version to now, from
 //               the published index + the delete log (block per listed document)
-//   k_co_rank / k_co_count / k_co_scan / k_co_write  the document at a past version (checkout): its
+//   k_co_rank / k_co_count / k_result_scan / k_co_write  the document at a past version (checkout): its
 //               items' orders and text, from the same inputs (block per listed document)
 //   k_pos_to_loc_at / k_loc_to_pos_at   the two lookups on a checked-out view (thread per query)
-//   k_blame / k_blame_scan  authorship runs of the current text, from the published index +
+//   k_blame / k_result_scan  authorship runs of the current text, from the published index +
 //               client_with_order (block per listed document)
 #pragma once
 #include "replay_core.h"
@@ -968,7 +968,7 @@ constexpr u32 DIFF_BAD = 1u;    // since > version, or a poisoned document: no r
 constexpr u32 DIFF_TEXT = 2u;   // ins_text was written (the document has content for all its orders)
 struct DiffRes {
   u32 n_pat, n_ins, flags, version;
-  u64 poff, ioff;  // first patch / first inserted item of this index in the result arrays (k_diff_scan)
+  u64 poff, ioff;  // first patch / first inserted item of this index in the result arrays (k_result_scan)
 };
 struct DiffIO {
   const u32* docs;     // [i] the listed documents
@@ -1045,42 +1045,57 @@ __global__ __launch_bounds__(DIFF_T) void k_diff_mark(Pools P, DiffIO D, u32 n, 
   }
 }
 
-// Exclusive scan of the indexes' patch and inserted-item counts into their result offsets (one
-// block; thread t takes a contiguous slice of the indexes); totals[0 / 1] = patches / items.
+// Exclusive scan of the indexes' result counts into their result offsets, shared by every result
+// pass (one block; thread t takes a contiguous slice of the indexes; thread 0 scans the slices'
+// sums serially); totals[j] = the sum of counter j over all indexes.  A result type Res with
+// SCAN_K<Res> counters gives its counts with scan_counts(res, c) -- 0 for an index without a
+// result, whether its count field is 0 (CoRes, BlameRes) or INVALID -- and takes its offsets
+// with scan_store(res, off); both stand next to the type.
 #define DIFF_SCAN_T 1024u
-__global__ __launch_bounds__(DIFF_SCAN_T) void k_diff_scan(DiffRes* res, u32 n, u64* totals) {
-  __shared__ u64 s_p[DIFF_SCAN_T], s_i[DIFF_SCAN_T];
+template <class Res>
+constexpr u32 SCAN_K = 1;
+template <class Res>
+__global__ __launch_bounds__(DIFF_SCAN_T) void k_result_scan(Res* res, u32 n, u64* totals) {
+  constexpr u32 K = SCAN_K<Res>;
+  __shared__ u64 s_a[K][DIFF_SCAN_T];
   u32 t = threadIdx.x;
   u32 per = (n + DIFF_SCAN_T - 1u) / DIFF_SCAN_T;
   u64 lo = min((u64)t * per, (u64)n), hi = min(lo + per, (u64)n);
-  u64 ap = 0, ai = 0;
-  for (u64 k = lo; k < hi; k++) { ap += res[k].n_pat; ai += res[k].n_ins; }
-  s_p[t] = ap;
-  s_i[t] = ai;
+  u64 a[K] = {}, c[K];
+  for (u64 k = lo; k < hi; k++) {
+    scan_counts(res[k], c);
+    for (u32 j = 0; j < K; j++) a[j] += c[j];
+  }
+  for (u32 j = 0; j < K; j++) s_a[j][t] = a[j];
   __syncthreads();
   if (t == 0) {
-    ap = ai = 0;
-    for (u32 x = 0; x < DIFF_SCAN_T; x++) {
-      u64 p = s_p[x], q = s_i[x];
-      s_p[x] = ap; s_i[x] = ai;
-      ap += p; ai += q;
+    for (u32 j = 0; j < K; j++) {
+      u64 s = 0;
+      for (u32 x = 0; x < DIFF_SCAN_T; x++) {
+        u64 p = s_a[j][x];
+        s_a[j][x] = s;
+        s += p;
+      }
+      totals[j] = s;
     }
-    totals[0] = ap;
-    totals[1] = ai;
   }
   __syncthreads();
-  ap = s_p[t];
-  ai = s_i[t];
+  for (u32 j = 0; j < K; j++) a[j] = s_a[j][t];
   for (u64 k = lo; k < hi; k++) {
-    u32 p = res[k].n_pat, q = res[k].n_ins;
-    res[k].poff = ap; res[k].ioff = ai;
-    ap += p; ai += q;
+    scan_counts(res[k], c);
+    scan_store(res[k], a);
+    for (u32 j = 0; j < K; j++) a[j] += c[j];
   }
 }
+// the diff's two counters: patches and inserted items
+template <>
+constexpr u32 SCAN_K<DiffRes> = 2;
+__device__ __forceinline__ void scan_counts(const DiffRes& r, u64* c) { c[0] = r.n_pat; c[1] = r.n_ins; }
+__device__ __forceinline__ void scan_store(DiffRes& r, const u64* off) { r.poff = off[0]; r.ioff = off[1]; }
 
 // One block per listed document, DIFF_T canonical spans per loop pass, in document order.
 // WRITE = false counts the document's patches and inserted items (res[i]); WRITE = true, after
-// k_diff_scan, writes them.  Within a pass each thread classifies its span (k, d, i above), wave
+// k_result_scan, writes them.  Within a pass each thread classifies its span (k, d, i above), wave
 // scans give the D / I items and patch starts before it, and the waves' totals meet in LDS; the
 // "is a patch open" state, the patch count and the D / I counts carry from pass to pass in
 // registers (every thread folds the same LDS totals).  The start span of patch p writes its pos,
@@ -1580,7 +1595,7 @@ constexpr u32 CO_BAD = 1u;    // version > the document's version, or a poisoned
 constexpr u32 CO_TEXT = 2u;   // text and digest were written (the document has content for all its orders)
 struct CoRes {
   u32 len, flags, version, at;  // old-visible items; CO_*; the document's version; v
-  u64 off;                      // first item of this index in ord / text (k_co_scan)
+  u64 off;                      // first item of this index in ord / text (k_result_scan)
   u64 digest;                   // text digest (text_hash per item, as k_materialize; 0 without content)
 };
 struct CoIO {
@@ -1701,33 +1716,9 @@ __global__ __launch_bounds__(DIFF_T) void k_co_count(Pools P, PubOut O, CoIO C, 
   if (tid == 0) C.res[i] = CoRes{carry, text ? CO_TEXT : 0u, no, v, 0ull, 0ull};
 }
 
-// Exclusive scan of the views' lengths into their offsets (one block; thread t takes a contiguous
-// slice of the indexes); *total = items of all views.
-__global__ __launch_bounds__(DIFF_SCAN_T) void k_co_scan(CoRes* res, u32 n, u64* total) {
-  __shared__ u64 s_a[DIFF_SCAN_T];
-  u32 t = threadIdx.x;
-  u32 per = (n + DIFF_SCAN_T - 1u) / DIFF_SCAN_T;
-  u64 lo = min((u64)t * per, (u64)n), hi = min(lo + per, (u64)n);
-  u64 a = 0;
-  for (u64 k = lo; k < hi; k++) a += res[k].len;  // (0 for an index without a result)
-  s_a[t] = a;
-  __syncthreads();
-  if (t == 0) {
-    a = 0;
-    for (u32 x = 0; x < DIFF_SCAN_T; x++) {
-      u64 p = s_a[x];
-      s_a[x] = a;
-      a += p;
-    }
-    *total = a;
-  }
-  __syncthreads();
-  a = s_a[t];
-  for (u64 k = lo; k < hi; k++) {
-    res[k].off = a;
-    a += res[k].len;
-  }
-}
+// k_result_scan's view of a CoRes: the view's length (0 for an index without a result)
+__device__ __forceinline__ void scan_counts(const CoRes& r, u64* c) { c[0] = r.len; }
+__device__ __forceinline__ void scan_store(CoRes& r, const u64* off) { r.off = off[0]; }
 
 // The views' items.  One block of CO_WAVES waves per index; wave w takes chunks w, w + CO_WAVES,
 // ... of 64 canonical spans (a chunk's items start at opos[k0], so chunks are independent, and
@@ -1887,7 +1878,7 @@ constexpr u32 BLAME_AGENT = 0u, BLAME_ID = 1u;  // CRDT_BLAME_*
 constexpr u32 BLAME_BAD = 1u;                   // a poisoned document: no result for this index
 struct BlameRes {
   u32 n_runs, flags;
-  u64 off;  // first run of this index in the result array (k_blame_scan)
+  u64 off;  // first run of this index in the result array (k_result_scan)
 };
 struct BlameIO {
   const u32* docs;  // [i] the listed documents
@@ -1926,7 +1917,7 @@ __device__ __forceinline__ u32 blame_walk(const CwoRun* cw, u32 ncwo, u32 r0, u3
 }
 
 // One block per listed document, DIFF_T canonical spans per loop pass, in document order, like
-// k_diff.  WRITE = false counts the document's runs (res[i]); WRITE = true, after k_blame_scan,
+// k_diff.  WRITE = false counts the document's runs (res[i]); WRITE = true, after k_result_scan,
 // writes them.  Each thread walks its span (blame_walk).  The tail of the last visible span
 // before it comes from the same wave (the highest visible lane below this one: a ballot and a
 // shuffle), from an earlier wave of the pass (LDS) or from an earlier pass (carried in registers:
@@ -2017,33 +2008,9 @@ __global__ __launch_bounds__(DIFF_T) void k_blame(Pools P, PubOut O, BlameIO B, 
   }
 }
 
-// Exclusive scan of the indexes' run counts into their offsets (k_co_scan's shape); *total = runs
-// of all indexes.
-__global__ __launch_bounds__(DIFF_SCAN_T) void k_blame_scan(BlameRes* res, u32 n, u64* total) {
-  __shared__ u64 s_a[DIFF_SCAN_T];
-  u32 t = threadIdx.x;
-  u32 per = (n + DIFF_SCAN_T - 1u) / DIFF_SCAN_T;
-  u64 lo = min((u64)t * per, (u64)n), hi = min(lo + per, (u64)n);
-  u64 a = 0;
-  for (u64 k = lo; k < hi; k++) a += res[k].n_runs;  // (0 for an index without a result)
-  s_a[t] = a;
-  __syncthreads();
-  if (t == 0) {
-    a = 0;
-    for (u32 x = 0; x < DIFF_SCAN_T; x++) {
-      u64 p = s_a[x];
-      s_a[x] = a;
-      a += p;
-    }
-    *total = a;
-  }
-  __syncthreads();
-  a = s_a[t];
-  for (u64 k = lo; k < hi; k++) {
-    res[k].off = a;
-    a += res[k].n_runs;
-  }
-}
+// k_result_scan's view of a BlameRes: its runs (0 for an index without a result)
+__device__ __forceinline__ void scan_counts(const BlameRes& r, u64* c) { c[0] = r.n_runs; }
+__device__ __forceinline__ void scan_store(BlameRes& r, const u64* off) { r.off = off[0]; }
 
 // pos -> loc for sorted query batches by merge path (BASELINE north_star's sorted batches): a
 // chunk of QBLK_Q queries that name one document, positions ascending, is merged against the

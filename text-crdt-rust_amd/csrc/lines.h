@@ -31,7 +31,7 @@ struct LineStart {
 struct LnRes {
   u32 n_lines;  // INVALID: no result for this index
   u32 pad_;
-  u64 off;      // first entry of this index in the table (k_ln_scan); it has n_lines + 1 entries
+  u64 off;      // first entry of this index in the table (k_result_scan); it has n_lines + 1 entries
 };
 struct LnIO {
   LnRes* res;      // [i]
@@ -143,35 +143,12 @@ __global__ __launch_bounds__(LN_T) void k_ln_count(EncIO E, LnIO Lo, u32 n) {
   if (tid == 0) Lo.res[i] = LnRes{s_c[0] + s_c[1] + s_c[2] + s_c[3] + 1u, 0u, 0ull};
 }
 
-// Exclusive scan of the indexes' entry counts (n_lines + 1: the sentinel) into their table offsets
-// (k_enc_scan's shape); *total = entries of all indexes.
-__global__ __launch_bounds__(DIFF_SCAN_T) void k_ln_scan(LnRes* res, u32 n, u64* total) {
-  __shared__ u64 s_a[DIFF_SCAN_T];
-  u32 t = threadIdx.x;
-  u32 per = (n + DIFF_SCAN_T - 1u) / DIFF_SCAN_T;
-  u64 lo = min((u64)t * per, (u64)n), hi = min(lo + per, (u64)n);
-  u64 a = 0;
-  for (u64 k = lo; k < hi; k++) a += res[k].n_lines == INVALID ? 0ull : (u64)res[k].n_lines + 1ull;
-  s_a[t] = a;
-  __syncthreads();
-  if (t == 0) {
-    a = 0;
-    for (u32 x = 0; x < DIFF_SCAN_T; x++) {
-      u64 p = s_a[x];
-      s_a[x] = a;
-      a += p;
-    }
-    *total = a;
-  }
-  __syncthreads();
-  a = s_a[t];
-  for (u64 k = lo; k < hi; k++) {
-    res[k].off = a;
-    a += res[k].n_lines == INVALID ? 0ull : (u64)res[k].n_lines + 1ull;
-  }
-}
+// k_result_scan's view of an LnRes: its table entries (n_lines + 1: the sentinel; an index without
+// a result counts as 0)
+__device__ __forceinline__ void scan_counts(const LnRes& r, u64* c) { c[0] = r.n_lines == INVALID ? 0ull : (u64)r.n_lines + 1ull; }
+__device__ __forceinline__ void scan_store(LnRes& r, const u64* off) { r.off = off[0]; }
 
-// Second sweep, after k_ln_scan: the same passes and rows.  Two running counts are carried from
+// Second sweep, after k_result_scan: the same passes and rows.  Two running counts are carried from
 // pass to pass in registers (every thread folds the same LDS values, as k_enc_count carries its
 // units): the breaks so far (the line number) and the char starts so far (the char position).
 // A dword has at most 4 of each and a pass at most 4,096, so both ride one wave scan per row as a
