@@ -214,6 +214,49 @@ int crdt_diff_counts(crdt_engine* e, uint32_t* n_patches, uint32_t* n_ins);
 int crdt_diff_read(crdt_engine* e, uint64_t i, crdt_patch* patches, uint32_t* ins_order, uint32_t* ins_text);
 int crdt_last_diff_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_materialize_ms */
 
+/* ---- text edits in units: the diff for a caller that keeps UTF-8 or UTF-16 text ------------------
+ * The diff above, restated in the units of "encoded text and unit offsets" below (enc is
+ * CRDT_ENC_UTF8: bytes, or CRDT_ENC_UTF16: uint16_t in host byte order), so that a Rust String, a
+ * JS string or an editor buffer can apply it without encoding the whole text.
+ *
+ * Take the item walk and the old-visible / new-visible classes of the diff for (docs[i], since[i])
+ * unchanged.  The width w(x) of the item with order x is the number of units crdt_encode_async
+ * writes for its content value (crdt_set_content) under enc, with the same rule: a value that is no
+ * Unicode scalar value counts, and is written, as U+FFFD.  Edit p is patch p of the diff:
+ *   pos, del_len, ins_len  the patch's;
+ *   unit       sum of w over the new-visible items before it: what crdt_pos_to_units answers for
+ *              pos on an encode of the current text;
+ *   del_units  sum of w over its old-only (deleted) items, which are in no current text;
+ *   ins_units  sum of w over its new-only (inserted) items;
+ *   ins_off    first unit of its inserted text in the index's inserted-unit pool = the ins_units
+ *              of the index's earlier edits;
+ *   reserved   0.
+ * The inserted-unit pool of an index is the concatenation, in patch order, of the encodings of
+ * every inserted item.  Applied front to back to the encoded text at since[i], each replacing
+ * del_units units at unit (an offset in the text the earlier edits left) with its ins_units units,
+ * the edits give the encoded current text.
+ *
+ * An index has no result (both counts 0xFFFFFFFF, crdt_edits_read returns CRDT_E_ARG, the other
+ * indexes are not affected) when since[i] is above the document's version, the document is
+ * poisoned, it has no content or a content stream shorter than its orders, or the sum of w over
+ * all its orders is 0xFFFFFFFF or more. */
+typedef struct { uint32_t pos, del_len, ins_len, unit, del_units, ins_units, ins_off, reserved; } crdt_edit;
+/* Compute the edits on the device, stream-ordered (publishes first if needed).  docs has no
+ * duplicates and enc is one of the two (CRDT_E_ARG).  Replaces the previous edits result; changes
+ * no document and none of the diff result, the checkout, the blame result, the encode result, the
+ * line index or the find result, and none of their calls touches the edits result;
+ * crdt_docs_alloc frees it.  The result is a copy: it stays readable whatever is replayed or
+ * published afterwards.  (The call waits once inside, for the two result totals.)  CRDT_E_NOMEM if
+ * an allocation fails: the engine stays usable, without an edits result, and the same call then
+ * succeeds. */
+int crdt_edits_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* since, int enc);
+/* Sizes of the last edits result, per docs[i] of that call (syncs); either may be NULL. */
+int crdt_edits_counts(crdt_engine* e, uint32_t* n_edits, uint32_t* n_ins_units);
+/* Result i: edits[n_edits[i]] and ins_units[n_ins_units[i]] (uint8_t or uint16_t by the call's enc);
+ * either may be NULL. */
+int crdt_edits_read(crdt_engine* e, uint64_t i, crdt_edit* edits, void* ins_units);
+int crdt_last_edits_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
+
 /* ---- documents at a past version: text and position queries --------------------------------
  * No reference counterpart (the reference keeps no history of its rope).  "The document at version
  * v" is the sequence of old-visible items of the definition above, in document order, for any

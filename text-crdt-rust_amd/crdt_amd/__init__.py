@@ -319,6 +319,10 @@ def lib():
     L.crdt_find_seek.argtypes = [vp, u64, P(u32), P(u32), C.c_int, P(u32)]
     L.crdt_find_seek_dev_async.argtypes = [vp, u64, vp, vp, C.c_int, vp]
     L.crdt_last_find_ms.argtypes = [vp, P(C.c_double)]
+    L.crdt_edits_async.argtypes = [vp, u64, P(u32), P(u32), C.c_int]
+    L.crdt_edits_counts.argtypes = [vp, P(u32), P(u32)]
+    L.crdt_edits_read.argtypes = [vp, u64, vp, vp]
+    L.crdt_last_edits_ms.argtypes = [vp, P(C.c_double)]
     L.crdt_last_error.restype = C.c_char_p
     L.crdt_trace_load.argtypes = [C.c_char_p, P(vp)]
     L.crdt_trace_parse.argtypes = [C.c_char_p, u64, P(vp)]
@@ -349,6 +353,7 @@ EXPORTED_SYMBOLS = [
     "crdt_lines_async", "crdt_line_counts", "crdt_lines_read", "crdt_pos_to_linecol", "crdt_linecol_to_pos",
     "crdt_pos_to_linecol_dev_async", "crdt_linecol_to_pos_dev_async", "crdt_last_lines_ms",
     "crdt_find_async", "crdt_find_counts", "crdt_find_read", "crdt_find_seek", "crdt_find_seek_dev_async", "crdt_last_find_ms",
+    "crdt_edits_async", "crdt_edits_counts", "crdt_edits_read", "crdt_last_edits_ms",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -739,6 +744,56 @@ class Engine:
         """device time of the last diff (HIP events)"""
         x = C.c_double()
         _check(self.L.crdt_last_diff_ms(self.h, C.byref(x)), "last_diff_ms")
+        return x.value
+
+    # --- text edits in units (crdt_gpu.h "text edits in units")
+    def edits_async(self, docs, since, enc="utf8"):
+        """compute the edits from version since[i] to now for docs[i] (no duplicates) on the device,
+        in units of enc ("utf8" / "utf16", or CRDT_ENC_UTF8 = 0 / CRDT_ENC_UTF16 = 1); replaces the
+        last edits result"""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        s = np.ascontiguousarray(since, dtype=np.uint32)
+        if d.shape != s.shape or d.ndim != 1:
+            raise ValueError("edits: docs and since are 1-d and of equal length")
+        enc = int(self.ENCODINGS.get(enc, enc))
+        _check(self.L.crdt_edits_async(self.h, d.shape[0], _p(d), _p(s), enc), "edits_async")
+        self._ed_n, self._ed_enc = d.shape[0], enc
+
+    def edits_counts(self):
+        """(n_edits, n_ins_units) per index of the last edits_async; 0xFFFFFFFF marks an index
+        without a result (since above the version, a poisoned document, one without content)"""
+        n = getattr(self, "_ed_n", 0)
+        ned, nun = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        _check(self.L.crdt_edits_counts(self.h, _p(ned), _p(nun)), "edits_counts")
+        return ned, nun
+
+    def edits_read(self, i: int, counts=None):
+        """result i of the last edits_async: (edits [n, 8] u32 = (pos, del_len, ins_len, unit,
+        del_units, ins_units, ins_off, 0), ins: np.uint8 (UTF-8) or np.uint16 (UTF-16) array);
+        raises CrdtError (rc=-100) for an index without a result"""
+        ned, nun = counts if counts is not None else self.edits_counts()
+        bad = not 0 <= i < len(ned) or int(ned[i]) == 0xFFFFFFFF  # (the library answers CRDT_E_ARG)
+        ed = np.zeros((0 if bad else int(ned[i]), 8), np.uint32)
+        ins = np.zeros(0 if bad else int(nun[i]), np.uint16 if getattr(self, "_ed_enc", 0) == 1 else np.uint8)
+        _check(self.L.crdt_edits_read(self.h, i, ed.ctypes.data, ins.ctypes.data), "edits_read")
+        return ed, ins
+
+    def edits(self, docs, since, enc="utf8", strict: bool = True):
+        """[(edits (n, 8) u32, ins np.uint8 | np.uint16)] per docs[i]: the edits that turn the encoded
+        text of docs[i] at version since[i] into its encoded current text.  An index without a result
+        raises CrdtError, or is None with strict=False; the other indexes are not affected."""
+        self.edits_async(docs, since, enc)
+        counts = self.edits_counts()
+        bad = np.flatnonzero(counts[0] == 0xFFFFFFFF)
+        if strict and bad.size:
+            raise CrdtError(f"edits failed rc=-100 for indexes {bad.tolist()}: since above the version, a poisoned "
+                            f"document, or one without content")
+        return [None if int(counts[0][i]) == 0xFFFFFFFF else self.edits_read(i, counts) for i in range(len(counts[0]))]
+
+    def edits_ms(self) -> float:
+        """device time of the last edits call (HIP events)"""
+        x = C.c_double()
+        _check(self.L.crdt_last_edits_ms(self.h, C.byref(x)), "last_edits_ms")
         return x.value
 
     # --- documents at a past version (crdt_gpu.h "documents at a past version")

@@ -18,6 +18,7 @@
 #include "encode.h"
 #include "lines.h"
 #include "find.h"
+#include "edits.h"
 
 using namespace crdt;
 
@@ -368,7 +369,7 @@ struct crdt_engine {
   // query scratch
   void* qbuf = nullptr;
   u64 qbuf_bytes = 0;
-  // The six result passes (ResultJob above; DESIGN.md "Result jobs"), each with the buffers of its
+  // The seven result passes (ResultJob above; DESIGN.md "Result jobs"), each with the buffers of its
   // own next to it, all kept and grown from call to call.
   // diff (crdt_diff_async): the listed documents, their versions to diff from and bitmap bases
   // (host copies live until the next call: they are the source of asynchronous uploads), the
@@ -411,8 +412,21 @@ struct crdt_engine {
   u32 fd_pat_h[FD_PAT_W] = {};
   DevBuf<u32> fd_pat;  // FD_PAT_W dwords: the pattern's units
   DevBuf<Match> fd_tab;
+  // text edits in units (crdt_edits_async): the diff's inputs on buffers of its own (the listed
+  // documents, their versions, bitmap bases and bitmaps), the width index (k_ed_prefix: one record
+  // per bitmap word) and the result arrays; the inserted-unit pool holds bytes or, by ed_mode,
+  // uint16_t units
+  ResultJob<EdRes, 2> ed;
+  std::vector<u32> ed_docs_h, ed_since_h;
+  std::vector<u64> ed_bm_h;
+  DevBuf<u32> ed_docs, ed_since, ed_bm;
+  DevBuf<EdWord> ed_words;
+  DevBuf<u64> ed_bm_base;
+  DevBuf<Edit> ed_edits;
+  DevBuf<u8> ed_units;
+  u32 ed_mode = 0;
   template <class F>
-  void each_job(F f) { f(diff); f(co); f(blame); f(enc); f(ln); f(fd); }
+  void each_job(F f) { f(diff); f(co); f(blame); f(enc); f(ln); f(fd); f(ed); }
 
   Pools pools_view(const PoolSet& ps) const {
     Pools p{};
@@ -480,6 +494,7 @@ struct crdt_engine {
     free_bufs(diff_docs, diff_since, diff_bm_base, diff_bm, diff_pat, diff_io, diff_it);
     free_bufs(co_docs, co_ver, co_bm_base, co_sp_base, co_bm, co_rk, co_opos, co_ord, co_text);
     free_bufs(blame_docs, blame_runs, enc_docs, enc_sp_base, enc_samples, enc_units, ln_tab, fd_pat, fd_tab);
+    free_bufs(ed_docs, ed_since, ed_bm_base, ed_bm, ed_words, ed_edits, ed_units);
   }
 
   int set_device() {
@@ -1467,6 +1482,86 @@ struct crdt_engine {
     return diff.stop();
   }
 
+  EdIO ed_view() const {
+    EdIO io{};
+    io.docs = ed_docs.p;
+    io.since = ed_since.p;
+    io.bm_base = ed_bm_base.p;
+    io.bm = ed_bm.p;
+    io.words = ed_words.p;
+    io.res = ed.res.p;
+    io.edits = ed_edits.p;
+    io.units = ed_units.p;
+    io.content = content;
+    io.cbase = cbase;
+    io.clen = clen;
+    return io;
+  }
+  // the kernels of one edits call, for one encoding (after the uploads and the start event)
+  template <u32 ENC>
+  int edits_sweeps(u64 n, u32 xw) {
+    Pools pv = pools_view(pools);
+    PubOut ov = pub_view();
+    DiffIO mark{};  // k_diff_mark reads these four only
+    mark.docs = ed_docs.p;
+    mark.since = ed_since.p;
+    mark.bm_base = ed_bm_base.p;
+    mark.bm = ed_bm.p;
+    hipLaunchKernelGGL(k_diff_mark, dim3((u32)n), dim3(DIFF_T), (size_t)xw * 4, stream, pv, mark, (u32)n, xw);
+    hipLaunchKernelGGL(k_ed_prefix<ENC>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ed_view(), (u32)n);
+    hipLaunchKernelGGL((k_edits<ENC, false>), dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, ed_view(), (u32)n);
+    hipLaunchKernelGGL(k_result_scan<EdRes>, dim3(1), dim3(DIFF_SCAN_T), 0, stream, ed.res.p, (u32)n, ed.tot.p);
+    int r = ed.read_totals();
+    if (!r) r = ed_edits.grow(stream, ed.tot_h[0]);
+    if (!r) r = ed_units.grow(stream, ed.tot_h[1] * (ENC == ENC_UTF8 ? 1u : 2u));
+    if (r) return r;
+    hipLaunchKernelGGL((k_edits<ENC, true>), dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, ed_view(), (u32)n);
+    return ed.stop();
+  }
+  // crdt_edits_async: mark the deletes below each version (k_diff_mark on the edits' own buffers),
+  // index the widths per bitmap word, count every document's edits and inserted units, scan the
+  // counts into offsets on the device, size the result arrays from the two totals (the one host
+  // read between the sweeps: 16 bytes), write the results.
+  int run_edits(u64 n, const uint32_t* dl, const uint32_t* since, u32 mode) {
+    int r = set_device();
+    if (r) return r;
+    ed.drop();
+    if (!published) {
+      r = publish();
+      if (r) return r;
+    }
+    ed_mode = mode;
+    r = ed.begin(n);
+    if (r) return r;
+    if (!n) {
+      ed.valid = true;
+      return 0;
+    }
+    ed_docs_h.assign(dl, dl + n);
+    ed_since_h.assign(since, since + n);
+    ed_bm_h.resize(n);
+    u64 words = 0;
+    u32 xw = 0;           // the largest listed bitmap that k_diff_mark builds in LDS
+    bool all_lds = true;  // ... and every listed one is (no bitmap word needs zeroing)
+    for (u64 i = 0; i < n; i++) {
+      ed_bm_h[i] = words;
+      u32 nw = pub_words(seg_h[dl[i]].ord_cap);
+      words += nw;
+      if (nw <= DIFF_MARK_WORDS) xw = std::max(xw, nw);
+      else all_lds = false;
+    }
+    r = grow_bufs(n, ed_docs, ed_since, ed_bm_base);
+    if (!r) r = grow_bufs(words, ed_bm, ed_words);
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(ed_docs.p, ed_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ed_since.p, ed_since_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ed_bm_base.p, ed_bm_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    r = ed.start();
+    if (r) return r;
+    if (!all_lds) HIPCHK(hipMemsetAsync(ed_bm.p, 0, words * 4, stream));
+    return mode == ENC_UTF8 ? edits_sweeps<ENC_UTF8>(n, xw) : edits_sweeps<ENC_UTF16>(n, xw);
+  }
+
   CoIO co_view() const {
     CoIO io{};
     io.docs = co_docs.p;
@@ -1773,6 +1868,7 @@ static_assert(ENC_UTF8 == CRDT_ENC_UTF8 && ENC_UTF16 == CRDT_ENC_UTF16, "CRDT_EN
 static_assert(sizeof(BlameRun) == sizeof(crdt_blame_run) && sizeof(crdt_blame_run) == 16, "crdt_blame_run is the kernels' BlameRun");
 static_assert(BLAME_AGENT == CRDT_BLAME_AGENT && BLAME_ID == CRDT_BLAME_ID, "CRDT_BLAME_* are the kernels' modes");
 static_assert(sizeof(Patch) == sizeof(crdt_patch) && sizeof(crdt_patch) == 16, "crdt_patch is the kernels' Patch");
+static_assert(sizeof(Edit) == sizeof(crdt_edit) && sizeof(crdt_edit) == 32, "crdt_edit is the kernels' Edit");
 
 static bool valid(const crdt_engine* e) { return e && e->n_docs > 0; }
 static bool poisoned(const crdt_engine* e) {
@@ -2625,6 +2721,7 @@ uint64_t crdt_mem_bytes(const crdt_engine* e) {
          buf_bytes(e->co.res, e->co_docs, e->co_ver, e->co_bm_base, e->co_sp_base, e->co_bm, e->co_rk, e->co_opos, e->co_ord, e->co_text) +
          buf_bytes(e->blame.res, e->blame_docs, e->blame_runs, e->enc.res, e->enc_docs, e->enc_sp_base, e->enc_samples, e->enc_units) +
          buf_bytes(e->ln.res, e->ln_tab, e->fd.res, e->fd_tab, e->fd_pat) +
+         buf_bytes(e->ed.res, e->ed_docs, e->ed_since, e->ed_bm_base, e->ed_bm, e->ed_words, e->ed_edits, e->ed_units) +
          e->n_docs * (sizeof(DocState) + sizeof(DocSeg) + 4 + 4 + 8);
 }
 
@@ -2742,6 +2839,49 @@ int crdt_diff_read(crdt_engine* e, uint64_t i, crdt_patch* patches, uint32_t* in
 }
 
 int crdt_last_diff_ms(crdt_engine* e, double* ms) { return job_ms(e, &crdt_engine::diff, ms); }
+
+int crdt_edits_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* since, int enc) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n_docs && (!docs || !since)) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
+  if (enc != CRDT_ENC_UTF8 && enc != CRDT_ENC_UTF16) {
+    g_last_error = "edits: enc is CRDT_ENC_UTF8 or CRDT_ENC_UTF16";
+    return CRDT_E_ARG;
+  }
+  return oom_as_nomem([&] { return e->run_edits(n_docs, docs, since, (u32)enc); });
+}
+
+int crdt_edits_counts(crdt_engine* e, uint32_t* n_edits, uint32_t* n_ins_units) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->ed.finish();
+  if (r) return r;
+  for (u64 i = 0; i < e->ed.n; i++) {
+    const EdRes& x = e->ed.res_h[i];
+    bool bad = (x.flags & ED_BAD) != 0;
+    if (n_edits) n_edits[i] = bad ? INVALID : x.n_ed;
+    if (n_ins_units) n_ins_units[i] = bad ? INVALID : x.n_units;
+  }
+  return 0;
+}
+
+int crdt_edits_read(crdt_engine* e, uint64_t i, crdt_edit* edits, void* ins_units) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->ed.finish();
+  if (r) return r;
+  if (i >= e->ed.n) return CRDT_E_ARG;
+  const EdRes& x = e->ed.res_h[i];
+  if (x.flags & ED_BAD) {
+    g_last_error = "edits: since above the document's version, a poisoned document, or one without content (or with too short a stream)";
+    return CRDT_E_ARG;
+  }
+  u64 usz = e->ed_mode == ENC_UTF8 ? 1u : 2u;
+  if (edits && x.n_ed) HIPCHK(hipMemcpy(edits, e->ed_edits.p + x.eoff, (u64)x.n_ed * sizeof(Edit), hipMemcpyDeviceToHost));
+  if (ins_units && x.n_units) HIPCHK(hipMemcpy(ins_units, e->ed_units.p + x.uoff * usz, (u64)x.n_units * usz, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int crdt_last_edits_ms(crdt_engine* e, double* ms) { return job_ms(e, &crdt_engine::ed, ms); }
 
 int crdt_checkout_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* version) {
   if (poisoned(e)) return CRDT_E_NOMEM;
