@@ -780,7 +780,19 @@ struct RemoteTxn { RemoteId id; std::vector<RemoteId> parents; std::vector<Remot
 
 struct Client { std::string name; std::vector<IoRun> item_orders; };
 
-struct Stats { u64 q2_triggers = 0; u64 integrate_iters = 0; u64 leaves_max = 0; };
+struct Stats {
+  u64 q2_triggers = 0; u64 integrate_iters = 0; u64 leaves_max = 0;
+  // integrate's scan, arm by arm (counted only: nothing below reads them)
+  u64 less = 0;         // the scan stopped on cmp(olc, left) < 0
+  u64 greater = 0;      // a step over an entry with cmp(olc, left) > 0
+  u64 tie_hi = 0;       // a tie, my name greater: scanning = false
+  u64 tie_same = 0;     // a tie, same origin_right: the scan stops
+  u64 tie_scan = 0;     // a tie that sets scanning = true and scan_start
+  u64 rewind = 0;       // scanning still set when the scan exits
+  u64 rewind_leaf = 0;  // a rewind whose scan_start is in another leaf than the exit cursor
+  u64 leaf_cross = 0;   // next_entry moved to another leaf
+  u64 max_cross = 0;    // the most leaf crossings within one integrate call
+};
 
 struct Doc {
   Tree tree;
@@ -882,6 +894,7 @@ struct Doc {
     Cursor left = cursor, scan_start = cursor;
     bool scanning = false;
     bool first = true;
+    u64 crossed = 0;
     while (true) {
       u32 other_order;
       if (!tree.get_item(cursor, other_order)) break;
@@ -892,7 +905,8 @@ struct Doc {
       Cursor olc;
       if (!get_cursor_after(other_left_order, olc)) return ERR_UNKNOWN_ID;
       int c = tree.cmp(olc, left);
-      if (c < 0) break;
+      if (c < 0) { stats.less++; break; }
+      if (c > 0) stats.greater++;
       if (c == 0) {
         u16 oa; u32 os;
         if (!order_to_loc(other_entry.order, oa, os)) return ERR_UNKNOWN_ID;
@@ -902,14 +916,21 @@ struct Doc {
         (void)first;
         const std::string& my = clients[agent].name;
         const std::string& other = clients[oa].name;
-        if (my > other) scanning = false;
-        else if (item.orr == other_entry.orr) break;
-        else { scanning = true; scan_start = cursor; }
+        if (my > other) { scanning = false; stats.tie_hi++; }
+        else if (item.orr == other_entry.orr) { stats.tie_same++; break; }
+        else { scanning = true; scan_start = cursor; stats.tie_scan++; }
       }
       first = false;
+      const Leaf* from = cursor.node;
       if (!tree.next_entry(cursor)) return ERR_NONTERMINATING;  // cursor unchanged => loops forever
+      if (cursor.node != from) { stats.leaf_cross++; crossed++; }
     }
-    if (scanning) cursor = scan_start;
+    if (crossed > stats.max_cross) stats.max_cross = crossed;
+    if (scanning) {
+      stats.rewind++;
+      if (scan_start.node != cursor.node) stats.rewind_leaf++;
+      cursor = scan_start;
+    }
     tree.insert(cursor, item);
     return OK;
   }

@@ -285,12 +285,23 @@ int64_t orc_text(void* h, const uint32_t* content, uint64_t clen, uint32_t* out,
   return (int64_t)t.size();
 }
 
-// stats: [q2_triggers, integrate_iters, n_leaves]
+// stats: [q2_triggers, integrate_iters, n_leaves, then integrate's scan arms (crdt_oracle.hpp Stats):
+// less, greater, tie_hi, tie_same, tie_scan, rewind, rewind_leaf, leaf_cross, max_cross] = 12 words
 void orc_stats(void* h, uint64_t* s) {
   Doc* d = (Doc*)h;
-  s[0] = d->stats.q2_triggers;
-  s[1] = d->stats.integrate_iters;
+  const Stats& t = d->stats;
+  s[0] = t.q2_triggers;
+  s[1] = t.integrate_iters;
   s[2] = d->tree.leaves.size();
+  s[3] = t.less;
+  s[4] = t.greater;
+  s[5] = t.tie_hi;
+  s[6] = t.tie_same;
+  s[7] = t.tie_scan;
+  s[8] = t.rewind;
+  s[9] = t.rewind_leaf;
+  s[10] = t.leaf_cross;
+  s[11] = t.max_cross;
 }
 
 // Double-delete RLE driver for the reference's inc_delete_range unit test.

@@ -4,7 +4,11 @@ random_local_trace: the reference's make_random_change (doc.rs:544-569): insert 
 len < 100 else 0.45; insert 1 char at U[0, len]; delete U[1, min(10, len-pos)] at U[0, len-1].
 concurrent_wire: several agents editing their own replicas (oracle) and exchanging remote txns;
 returns one causally ordered wire batch that replays the whole history.
+gossip_log / causal_shuffle / gossip_family: partially delivered concurrent histories (every agent
+pulls from one peer at a time) and seeded causal reorderings of them.
 """
+import bisect
+import functools
 import os
 import random
 import struct
@@ -203,6 +207,167 @@ def config5_wire(seed: int, base_len: int = 4096, n_agents: int = 16, rounds: in
             txns.append(per_agent[a].pop(0))
         frontier = [(a, seq[a] - 1) for a in names]
     return build_wire(txns)
+
+
+def gossip_log(seed: int, n_agents: int = 4, steps: int = 200, base_len: int = 16, p_edit: float = 0.7,
+               p_ins: float = 0.65, ins_max: int = 3, hot=None, leaf: int = 32, del_max: int = 1):
+    """A concurrent history with partial delivery: A may have seen B's txns but not C's.
+
+    Every agent edits an oracle replica of its own (layout `leaf`) and a set records which txns it
+    knows.  Agent 0 inserts `base_len` chars and everyone receives that txn.  Then `steps` times a
+    random agent either (probability `p_edit`) makes one local single-op txn, recorded through the
+    oracle's local->remote recorder like concurrent_wire's record2, or pulls from one random peer:
+    every txn the peer knows and it does not, in log order, as one remote batch.  An edit is an
+    insert of 1..`ins_max` chars with probability `p_ins`, at a position in [0, len-1] (with
+    probability 0.7 one of the absolute positions `hot`, clamped to len-1), else a delete of
+    1..`del_max` chars at a position in [0, len-2].  So an insert's origins are often another
+    agent's items that a third agent has not seen, agents first appear at a receiver in the middle
+    of a history, and integrate's scan meets entries left and right of the new item's origin_left.
+
+    Two restrictions, both limits of the reference that the oracle restates:
+      - no insert at the document's end: concurrent scans would run off the document
+        (ERR_NONTERMINATING, as in test_error_statuses_match);
+      - `del_max` = 1 by default: a remote delete of several items assumes their orders are
+        contiguous at the receiver, and under partial delivery they are not (ERR_UNKNOWN_ID).  With
+        `del_max` > 1 some histories stop with an error status; if a pull fails during generation
+        the history is truncated there, as concurrent_wire does.
+
+    Returns the parsed txn log in creation order, which is one causal order.  Delivery orders do
+    NOT converge in the restated reference: the final id sequence of one history differs between
+    causal orders (entry merging depends on arrival order).  The engine's contract
+    is bit-exactness against the oracle for EACH order; do not add a convergence check here."""
+    from oracle_lib import OracleDoc, lib, _p
+    import ctypes as C
+    rng = random.Random(seed)
+    L = lib()
+    names = [f"g{rng.randrange(1 << 16):04x}{i}" for i in range(n_agents)]
+    reps = [OracleDoc(leaf, 16 if leaf == 32 else 8) for _ in range(n_agents)]
+    ids = [None] * n_agents
+    known = [set() for _ in range(n_agents)]
+    log = []
+    buf = C.create_string_buffer(1 << 16)
+
+    def record(i, op):
+        if ids[i] is None:
+            ids[i] = reps[i].agent(names[i])
+        c = np.array([1], np.uint32)
+        p = np.array([op], np.uint32).reshape(-1, 3)
+        n = L.orc_local_trace_to_wire(reps[i].h, ids[i], 1, _p(c), _p(p), C.cast(buf, C.c_void_p), 1 << 16)
+        assert n > 0, (n, seed, op)
+        for t in parse_wire(buf.raw[:n])[1]:
+            known[i].add(len(log))
+            log.append(t)
+
+    record(0, (0, 0, base_len))
+    for i in range(1, n_agents):
+        assert reps[i].apply_remote_wire(build_wire(log)) == 0
+        known[i] |= known[0]
+    for _ in range(steps):
+        i = rng.randrange(n_agents)
+        if rng.random() < p_edit:
+            n = len(reps[i])
+            if n < 2 or rng.random() < p_ins:
+                if hot and rng.random() < 0.7:
+                    pos = min(rng.choice(hot), n - 1)
+                else:
+                    pos = rng.randint(0, n - 1)
+                record(i, (pos, 0, rng.randint(1, ins_max)))
+            else:
+                pos = rng.randint(0, n - 2)
+                record(i, (pos, rng.randint(1, min(del_max, n - 1 - pos)), 0))
+        else:
+            j = rng.choice([k for k in range(n_agents) if k != i])
+            new = sorted(known[j] - known[i])
+            if new:
+                if reps[i].apply_remote_wire(build_wire([log[k] for k in new])) != 0:
+                    return log
+                known[i] |= known[j]
+    return log
+
+
+def causal_deps(log):
+    """Per txn of a parsed log, the set of log indexes it depends on: the txns holding its parents,
+    its agent's previous txn (the one whose seq range ends where this one starts), and the txns
+    holding every id its ops name -- both origins of an insert, every item of a delete's target."""
+    starts, owners = {}, {}
+    for k, (a, s, _ps, _ops) in enumerate(log):
+        starts.setdefault(a, []).append(s)  # (an agent's txns appear in seq order in any causal log)
+        owners.setdefault(a, []).append(k)
+
+    def owner(a, s):
+        return owners[a][bisect.bisect_right(starts[a], s) - 1]
+    deps = []
+    for k, (a, s, ps, ops) in enumerate(log):
+        d = set()
+        for pn, pq in ps:
+            if pn != "ROOT":
+                d.add(owner(pn, pq))
+        if s > 0:
+            d.add(owner(a, s - 1))
+        for kind, an, asq, bn, bsq, ln in ops:
+            if kind == 0:
+                for nm, sq in ((an, asq), (bn, bsq)):
+                    if nm != "ROOT":
+                        d.add(owner(nm, sq))
+            else:
+                d.update(owner(an, asq + j) for j in range(ln))
+        d.discard(k)
+        deps.append(d)
+    return deps
+
+
+def causal_shuffle(log, seed: int):
+    """A seeded random topological order of a parsed log under causal_deps: a permutation of the
+    log that every replica could have received.  (The replayed state depends on the order; see
+    gossip_log.)"""
+    rng = random.Random(seed)
+    deps = causal_deps(log)
+    waiting = [len(d) for d in deps]
+    children = [[] for _ in log]
+    for k, d in enumerate(deps):
+        for x in d:
+            children[x].append(k)
+    ready = [k for k, w in enumerate(waiting) if w == 0]
+    out = []
+    while ready:
+        i = rng.randrange(len(ready))
+        ready[i], ready[-1] = ready[-1], ready[i]
+        k = ready.pop()
+        out.append(log[k])
+        for c in children[k]:
+            waiting[c] -= 1
+            if waiting[c] == 0:
+                ready.append(c)
+    assert len(out) == len(log)
+    return out
+
+
+# the gossip families of tests/test_gossip_ref.py, tests/test_emu_parity.py and tests/test_gpu_gossip.py
+# (all: p_ins 0.65, ins_max 3).  A: small; B: three hotspots; D: two hotspots, 8 agents, edit-heavy:
+# the deep scans; E: 70 agents, past the 64 name ranks kept in LDS and the 25 frontier heads kept
+# in lanes; X: B with deletes of 1..4 items: the family whose histories can stop with an error.
+GOSSIP_FAMILIES = {
+    "A": dict(n_agents=4, steps=300, base_len=16),
+    "B": dict(n_agents=6, steps=600, hot=[3, 7, 11], p_edit=0.8),
+    "D": dict(n_agents=8, steps=1500, hot=[2, 9], p_edit=0.85, base_len=12),
+    "E": dict(n_agents=70, steps=2500, hot=[4], p_edit=0.8),
+    "X": dict(n_agents=6, steps=600, hot=[3, 7, 11], p_edit=0.8, del_max=4),
+}
+GOSSIP_SEEDS = {"A": range(4), "B": range(4), "D": range(4), "E": range(4), "X": range(4)}
+GOSSIP_ORDERS = 3  # the log order and two causal shuffles
+
+
+@functools.lru_cache(maxsize=None)
+def gossip_family(name: str):
+    """Every history of a family as wire batches: [(seed, order, wire)], order 0 = the log order,
+    1 and 2 = causal shuffles; generated once per process."""
+    out = []
+    for seed in GOSSIP_SEEDS[name]:
+        log = gossip_log(seed, **GOSSIP_FAMILIES[name])
+        out.append((seed, 0, build_wire(log)))
+        for k in range(1, GOSSIP_ORDERS):
+            out.append((seed, k, build_wire(causal_shuffle(log, 1000 * k + seed))))
+    return out
 
 
 def config1_probes(counts, patches, agent: int, seed=None):

@@ -17,6 +17,9 @@ LIB_PATH = os.path.join(ORACLE_DIR, "build", "liboracle.so")
 OK, ERR_POS_OOB, ERR_SEQ, ERR_UNKNOWN_AGENT, ERR_UNKNOWN_ID, ERR_NONTERMINATING = 0, -1, -2, -3, -4, -5
 ERR_CAPACITY, ERR_EMPTY_TXN, ERR_FRONTIER, ERR_BAD_INPUT = -6, -7, -8, -9
 
+STAT_KEYS = ("q2_triggers", "integrate_iters", "leaves_alloc", "less", "greater", "tie_hi", "tie_same", "tie_scan",
+             "rewind", "rewind_leaf", "leaf_cross", "max_cross")
+
 _lib = None
 
 
@@ -192,9 +195,13 @@ class OracleDoc:
         return pos, dl
 
     def stats(self) -> dict:
-        s = np.zeros(3, np.uint64)
+        """q2_triggers, integrate_iters, leaves_alloc, and integrate's scan counted arm by arm
+        (crdt_oracle.hpp Stats): less / greater / tie_hi / tie_same / tie_scan per visited entry,
+        rewind (scanning set at exit), rewind_leaf (scan_start in another leaf than the exit
+        cursor), leaf_cross (next_entry changed leaf), max_cross (most crossings in one scan)."""
+        s = np.zeros(len(STAT_KEYS), np.uint64)
         self.L.orc_stats(self.h, _p(s, C.c_uint64))
-        return dict(q2_triggers=int(s[0]), integrate_iters=int(s[1]), leaves_alloc=int(s[2]))
+        return {k: int(v) for k, v in zip(STAT_KEYS, s)}
 
 
 def trace_to_wire(counts, patches, agent_name: str = "jeremy", leaf_cap: int = 32) -> bytes:

@@ -274,3 +274,22 @@ def test_wide_frontier(seed):
     e = EmuDoc(32)
     assert e.run_wire_local(w, "local-editor", c, pt, 48) == 0
     assert diff_states(o.export(), e.export()) == []
+
+
+@pytest.mark.parametrize("L", [32, 4])
+@pytest.mark.parametrize("fam", ["A", "B", "D", "E", "X"])
+def test_gossip_histories(fam, L):
+    # partially delivered histories in three causal orders each (fuzz_gen.gossip_log): integrate's
+    # scan takes its Less and Greater arms, rewinds into other leaves and crosses dozens of them
+    # (tests/test_gossip_ref.py asserts that on the oracle's counters); family E has 70 agents and
+    # frontiers past the lanes, family X histories that stop with an error status
+    from fuzz_gen import gossip_family
+    for seed, k, w in gossip_family(fam):
+        o = OracleDoc(L, 16 if L == 32 else 8)
+        so = o.apply_remote_wire(w)
+        e = EmuDoc(L)
+        se = e.run_wire(w, 48)
+        assert so == se, (seed, k, so, se)
+        if so == 0:
+            assert e.check() == "", (seed, k)
+            assert diff_states(o.export(), e.export()) == [], (seed, k)
