@@ -498,6 +498,69 @@ int crdt_find_seek_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, co
                              uint32_t* k);
 int crdt_last_find_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
 
+/* ---- rebase: map positions between a past version and the current text ---------------------------
+ * A caller of the diff or the edits holds things that point into the old text (cursors, selections,
+ * diagnostics, breakpoints, find matches) and has to move them to where they now stand, or to ask
+ * the reverse ("which old offset does this new one come from").  A rebase map is built from the
+ * last diff result (CRDT_REBASE_FROM_DIFF) or the last edits result (CRDT_REBASE_FROM_EDITS):
+ * index i of the map is index i of that call.
+ *
+ *  - Take index i's patches P_0 .. P_{m-1} (pos, del_len, ins_len).  The char table has one span
+ *    per patch:
+ *      new_at[p] = pos[p], new_len[p] = ins_len[p], old_len[p] = del_len[p],
+ *      old_at[p] = pos[p] - (sum of ins_len[q], q < p) + (sum of del_len[q], q < p):
+ *    where the patch starts in the text at since[i].
+ *  - The units table is the same with unit, del_units, ins_units of the edits.  It exists only for
+ *    an edits source, in that call's encoding.
+ *  - Spans are ascending on both sides, and neighbouring spans are at least one kept item apart.
+ *  - A query is (idx, x, kind, dir, bias).  kind picks the table.  CRDT_REBASE_OLD_TO_NEW reads
+ *    each span as (a, la, b, lb) = (old_at, old_len, new_at, new_len); CRDT_REBASE_NEW_TO_OLD swaps
+ *    the two sides.  x is a cursor position: the gap before item x of the source side's text.
+ *  - Let k be the last span with a[k] <= x.
+ *      no such span:   y = x, hit = 0;
+ *      x > a + la:     y = x - (a + la) + (b + lb), hit = 0;
+ *      otherwise:      y = b if side < 0, else b + lb; hit = 1 iff a < x < a + la.
+ *    side = bias (CRDT_BIAS_LEFT: -1, CRDT_BIAS_RIGHT: +1) when la == 0, a pure insertion on the
+ *    other side; otherwise -1 at x == a, +1 at x == a + la, and bias strictly inside.  hit == 1
+ *    means x was strictly inside a stretch that does not exist on the other side.  (The mapping
+ *    rule of ProseMirror's StepMap.map.)
+ *  - x is not checked against the length of either text, as crdt_find_seek does not check pos: the
+ *    answer is a function of the table alone, in arithmetic modulo 2^32.
+ *  - With OLD_TO_NEW, BIAS_RIGHT and x the index of an item visible in both texts: hit == 0 and y
+ *    is that item's index in the current text; NEW_TO_OLD with BIAS_RIGHT maps y back to x.  For
+ *    fixed dir and bias y is non-decreasing in x, and the left answer is <= the right answer. */
+enum { CRDT_REBASE_FROM_DIFF = 0, CRDT_REBASE_FROM_EDITS = 1 };
+enum { CRDT_REBASE_CHARS = 0, CRDT_REBASE_UNITS = 1 };
+enum { CRDT_REBASE_OLD_TO_NEW = 0, CRDT_REBASE_NEW_TO_OLD = 1 };
+enum { CRDT_BIAS_LEFT = 0, CRDT_BIAS_RIGHT = 1 };
+typedef struct { uint32_t old_at, old_len, new_at, new_len; } crdt_rebase_span;
+/* Build the map on the device, stream-ordered, from the named source.  CRDT_E_ARG for an unknown
+ * src and when the source has no valid result.  Replaces the previous map.  The map is a copy: it
+ * stays valid whatever is diffed, replayed, published or encoded afterwards, until the next call
+ * or crdt_docs_alloc.  Changes no document and none of the other results, and none of their calls
+ * touches the map.  No host wait inside: the tables are sized by the source's totals, which the
+ * host holds since that call.  CRDT_E_NOMEM if an allocation fails: the engine stays usable,
+ * without a map and with the source intact, and the same call then succeeds. */
+int crdt_rebase_async(crdt_engine* e, int src);
+/* Spans per index of the source call (syncs).  An index the source has no result for has none
+ * here: its count is 0xFFFFFFFF, reading it returns CRDT_E_ARG, and a host-form query that names it
+ * returns CRDT_E_ARG for the whole call and writes nothing (as does an idx out of range). */
+int crdt_rebase_counts(crdt_engine* e, uint32_t* n_spans);
+/* The n_spans[i] spans of index i in chars or in units (spans may be NULL when there are none).
+ * CRDT_E_ARG for an unknown kind, and for CRDT_REBASE_UNITS on a map built from a diff. */
+int crdt_rebase_read(crdt_engine* e, uint64_t i, int kind, crdt_rebase_span* spans);
+/* The mapping (above); idx[q] names an index of the map; hit may be NULL.  CRDT_E_ARG for an unknown
+ * kind, dir or bias, for CRDT_REBASE_UNITS on a map built from a diff, and before any map.  n == 0
+ * is a no-op. */
+int crdt_rebase(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* x, int kind, int dir, int bias,
+                uint32_t* y, uint8_t* hit);
+/* Device-pointer form (inputs/outputs already in HBM; async on the engine stream).  idx cannot be
+ * checked on the host: a query whose idx is out of range or has no result is answered 0xFFFFFFFF,
+ * with hit = 0. */
+int crdt_rebase_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* x, int kind, int dir,
+                          int bias, uint32_t* y, uint8_t* hit);
+int crdt_last_rebase_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_last_diff_ms */
+
 /* ListCRDT::len (doc.rs:484-486) */
 int crdt_doc_len(crdt_engine* e, uint64_t n, const uint32_t* doc, uint32_t* len);
 int crdt_doc_status(crdt_engine* e, int32_t* status /* n_docs */);

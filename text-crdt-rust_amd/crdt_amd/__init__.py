@@ -323,6 +323,12 @@ def lib():
     L.crdt_edits_counts.argtypes = [vp, P(u32), P(u32)]
     L.crdt_edits_read.argtypes = [vp, u64, vp, vp]
     L.crdt_last_edits_ms.argtypes = [vp, P(C.c_double)]
+    L.crdt_rebase_async.argtypes = [vp, C.c_int]
+    L.crdt_rebase_counts.argtypes = [vp, P(u32)]
+    L.crdt_rebase_read.argtypes = [vp, u64, C.c_int, vp]
+    L.crdt_rebase.argtypes = [vp, u64, P(u32), P(u32), C.c_int, C.c_int, C.c_int, P(u32), P(C.c_uint8)]
+    L.crdt_rebase_dev_async.argtypes = [vp, u64, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.crdt_last_rebase_ms.argtypes = [vp, P(C.c_double)]
     L.crdt_last_error.restype = C.c_char_p
     L.crdt_trace_load.argtypes = [C.c_char_p, P(vp)]
     L.crdt_trace_parse.argtypes = [C.c_char_p, u64, P(vp)]
@@ -354,6 +360,7 @@ EXPORTED_SYMBOLS = [
     "crdt_pos_to_linecol_dev_async", "crdt_linecol_to_pos_dev_async", "crdt_last_lines_ms",
     "crdt_find_async", "crdt_find_counts", "crdt_find_read", "crdt_find_seek", "crdt_find_seek_dev_async", "crdt_last_find_ms",
     "crdt_edits_async", "crdt_edits_counts", "crdt_edits_read", "crdt_last_edits_ms",
+    "crdt_rebase_async", "crdt_rebase_counts", "crdt_rebase_read", "crdt_rebase", "crdt_rebase_dev_async", "crdt_last_rebase_ms",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -1107,6 +1114,55 @@ class Engine:
         _check(self.L.crdt_last_find_ms(self.h, C.byref(x)), "last_find_ms")
         return x.value
 
+    # --- rebase: positions between a past version and the current text (crdt_gpu.h "rebase")
+    REBASE_SRCS = {"diff": 0, "edits": 1}
+    REBASE_KINDS = {"chars": 0, "units": 1}
+    REBASE_DIRS = {"old_to_new": 0, "new_to_old": 1}
+    BIASES = {"left": 0, "right": 1}
+
+    def rebase_async(self, src="diff"):
+        """build the rebase map on the device from the last diff ("diff") or the last edits result
+        ("edits", which also gives the unit table); replaces the last map"""
+        src = int(self.REBASE_SRCS.get(src, src))
+        _check(self.L.crdt_rebase_async(self.h, src), "rebase_async")
+        self._rb_n = getattr(self, "_ed_n" if src == 1 else "_diff_n", 0)
+
+    def rebase_counts(self) -> np.ndarray:
+        """spans per index of the map's source call; 0xFFFFFFFF marks an index without a result"""
+        out = np.zeros(getattr(self, "_rb_n", 0), np.uint32)
+        _check(self.L.crdt_rebase_counts(self.h, _p(out)), "rebase_counts")
+        return out
+
+    def rebase_read(self, i: int, kind="chars", counts=None) -> np.ndarray:
+        """the spans of index i: [n_spans, 4] u32 = (old_at, old_len, new_at, new_len), in "chars" or
+        in "units"; raises CrdtError (rc=-100) for an index without a result"""
+        counts = counts if counts is not None else self.rebase_counts()
+        bad = not 0 <= i < len(counts) or int(counts[i]) == 0xFFFFFFFF  # (the library answers CRDT_E_ARG)
+        out = np.zeros((0 if bad else int(counts[i]), 4), np.uint32)
+        _check(self.L.crdt_rebase_read(self.h, i, int(self.REBASE_KINDS.get(kind, kind)), out.ctypes.data if out.size else None),
+               "rebase_read")
+        return out
+
+    def rebase(self, idx, x, kind="chars", dir="old_to_new", bias="right"):
+        """(y, hit): position x[q] of index idx[q]'s old text mapped into its current text
+        ("old_to_new") or back ("new_to_old"), in "chars" or "units"; bias "left" / "right" decides
+        at an insertion and inside a replaced stretch, where hit is 1"""
+        i = np.ascontiguousarray(idx, dtype=np.uint32)
+        p = np.ascontiguousarray(x, dtype=np.uint32)
+        if i.shape != p.shape or i.ndim != 1:
+            raise ValueError("rebase: idx and x are 1-d and of equal length")
+        y, hit = np.zeros(p.shape[0], np.uint32), np.zeros(p.shape[0], np.uint8)
+        _check(self.L.crdt_rebase(self.h, p.shape[0], _p(i), _p(p), int(self.REBASE_KINDS.get(kind, kind)),
+                                  int(self.REBASE_DIRS.get(dir, dir)), int(self.BIASES.get(bias, bias)), _p(y),
+                                  _p(hit, C.c_uint8)), "rebase")
+        return y, hit
+
+    def rebase_ms(self) -> float:
+        """device time of the last rebase_async (HIP events)"""
+        x = C.c_double()
+        _check(self.L.crdt_last_rebase_ms(self.h, C.byref(x)), "last_rebase_ms")
+        return x.value
+
     def timings(self):
         a, b = C.c_double(), C.c_double()
         self.L.crdt_last_timings(self.h, C.byref(a), C.byref(b))
@@ -1154,6 +1210,14 @@ class ListCRDT:
         """(patches [n, 4] u32 = (pos, del_len, ins_len, ins_off), ins_order, ins_text or None): what
         turns the text at version `v` (an earlier version()) into the current text"""
         return self.e.diff([0], [v])[0]
+
+    def rebase_since(self, v: int, positions, dir: str = "old_to_new", bias: str = "right"):
+        """(y, hit): char positions of the text at version `v` (an earlier version()) moved to where
+        they stand in the current text, or back with dir "new_to_old" (Engine.rebase)"""
+        self.e.diff([0], [v])
+        self.e.rebase_async("diff")
+        p = np.ascontiguousarray(positions, dtype=np.uint32)
+        return self.e.rebase(np.zeros(p.shape[0], np.uint32), p, "chars", dir, bias)
 
     def text_at(self, v: int) -> np.ndarray:
         """the text (UTF-32 code points) at version `v` (an earlier version(); needs set_content)"""

@@ -19,6 +19,7 @@
 #include "lines.h"
 #include "find.h"
 #include "edits.h"
+#include "rebase.h"
 
 using namespace crdt;
 
@@ -369,7 +370,7 @@ struct crdt_engine {
   // query scratch
   void* qbuf = nullptr;
   u64 qbuf_bytes = 0;
-  // The seven result passes (ResultJob above; DESIGN.md "Result jobs"), each with the buffers of its
+  // The eight result passes (ResultJob above; DESIGN.md "Result jobs"), each with the buffers of its
   // own next to it, all kept and grown from call to call.
   // diff (crdt_diff_async): the listed documents, their versions to diff from and bitmap bases
   // (host copies live until the next call: they are the source of asynchronous uploads), the
@@ -425,8 +426,14 @@ struct crdt_engine {
   DevBuf<Edit> ed_edits;
   DevBuf<u8> ed_units;
   u32 ed_mode = 0;
+  // rebase map (crdt_rebase_async): span tables copied from the diff or the edits result (rb_src),
+  // at the source's per-index offsets; the unit table exists after an edits source only.  No
+  // other call reads or writes these buffers, so the map outlives its source.
+  ResultJob<RbRes> rb;
+  DevBuf<RbSpan> rb_ch, rb_un;
+  u32 rb_src = 0;
   template <class F>
-  void each_job(F f) { f(diff); f(co); f(blame); f(enc); f(ln); f(fd); f(ed); }
+  void each_job(F f) { f(diff); f(co); f(blame); f(enc); f(ln); f(fd); f(ed); f(rb); }
 
   Pools pools_view(const PoolSet& ps) const {
     Pools p{};
@@ -494,7 +501,7 @@ struct crdt_engine {
     free_bufs(diff_docs, diff_since, diff_bm_base, diff_bm, diff_pat, diff_io, diff_it);
     free_bufs(co_docs, co_ver, co_bm_base, co_sp_base, co_bm, co_rk, co_opos, co_ord, co_text);
     free_bufs(blame_docs, blame_runs, enc_docs, enc_sp_base, enc_samples, enc_units, ln_tab, fd_pat, fd_tab);
-    free_bufs(ed_docs, ed_since, ed_bm_base, ed_bm, ed_words, ed_edits, ed_units);
+    free_bufs(ed_docs, ed_since, ed_bm_base, ed_bm, ed_words, ed_edits, ed_units, rb_ch, rb_un);
   }
 
   int set_device() {
@@ -1857,7 +1864,47 @@ struct crdt_engine {
     else hipLaunchKernelGGL(k_find_write<ENC_UTF16>, dim3((u32)n), dim3(LN_T), 0, stream, ev, fd_view(), pt, (u32)n);
     return fd.stop();
   }
+
+  RbIO rb_view(u64 cap) const {
+    RbIO io{};
+    io.res = rb.res.p;
+    io.ch = rb_ch.p;
+    io.un = rb_un.p;
+    io.cap = cap;
+    return io;
+  }
+  // crdt_rebase_async: copy the source's patch lists into span tables, one block per index.  The
+  // tables take the source's per-index offsets and its total (tot_h, read when the source was
+  // computed), so there is no scan and no host wait here.
+  int run_rebase(u32 src) {
+    int r = set_device();
+    if (r) return r;
+    u64 n = src == RB_FROM_DIFF ? diff.n : ed.n;
+    u64 total = !n ? 0 : src == RB_FROM_DIFF ? diff.tot_h[0] : ed.tot_h[0];
+    rb_src = src;
+    r = rb.begin(n);
+    if (r) return r;
+    if (!n) {
+      rb.valid = true;
+      return 0;
+    }
+    r = rb_ch.grow(stream, total);
+    if (!r && src == RB_FROM_EDITS) r = rb_un.grow(stream, total);
+    if (r) return r;
+    r = rb.start();
+    if (r) return r;
+    if (src == RB_FROM_DIFF)
+      hipLaunchKernelGGL(k_rebase_build<RbDiffSrc>, dim3((u32)n), dim3(RB_T), 0, stream, RbDiffSrc{diff.res.p, diff_pat.p}, rb_view(total), (u32)n);
+    else
+      hipLaunchKernelGGL(k_rebase_build<RbEditSrc>, dim3((u32)n), dim3(RB_T), 0, stream, RbEditSrc{ed.res.p, ed_edits.p}, rb_view(total), (u32)n);
+    return rb.stop();
+  }
 };
+static_assert(RB_FROM_DIFF == CRDT_REBASE_FROM_DIFF && RB_FROM_EDITS == CRDT_REBASE_FROM_EDITS, "CRDT_REBASE_FROM_* are the kernels' sources");
+static_assert(RB_CHARS == CRDT_REBASE_CHARS && RB_UNITS == CRDT_REBASE_UNITS, "CRDT_REBASE_CHARS / _UNITS are the kernels' kinds");
+static_assert(RB_OLD_TO_NEW == CRDT_REBASE_OLD_TO_NEW && RB_NEW_TO_OLD == CRDT_REBASE_NEW_TO_OLD, "CRDT_REBASE_*_TO_* are the kernels' directions");
+static_assert(RB_LEFT == CRDT_BIAS_LEFT && RB_RIGHT == CRDT_BIAS_RIGHT, "CRDT_BIAS_* are the kernels' biases");
+static_assert(sizeof(RbSpan) == sizeof(crdt_rebase_span) && sizeof(crdt_rebase_span) == 16, "crdt_rebase_span is the kernels' RbSpan");
 static_assert(FIND_ICASE == CRDT_FIND_ASCII_ICASE && FD_MAX_CHARS == CRDT_FIND_MAX_CHARS, "CRDT_FIND_* are the kernels' flag and limit");
 static_assert(SEEK_NEXT == CRDT_SEEK_NEXT && SEEK_PREV == CRDT_SEEK_PREV, "CRDT_SEEK_* are the kernels' directions");
 static_assert(sizeof(Match) == sizeof(crdt_match) && sizeof(crdt_match) == 8, "crdt_match is the kernels' Match");
@@ -2722,6 +2769,7 @@ uint64_t crdt_mem_bytes(const crdt_engine* e) {
          buf_bytes(e->blame.res, e->blame_docs, e->blame_runs, e->enc.res, e->enc_docs, e->enc_sp_base, e->enc_samples, e->enc_units) +
          buf_bytes(e->ln.res, e->ln_tab, e->fd.res, e->fd_tab, e->fd_pat) +
          buf_bytes(e->ed.res, e->ed_docs, e->ed_since, e->ed_bm_base, e->ed_bm, e->ed_words, e->ed_edits, e->ed_units) +
+         buf_bytes(e->rb.res, e->rb_ch, e->rb_un) +
          e->n_docs * (sizeof(DocState) + sizeof(DocSeg) + 4 + 4 + 8);
 }
 
@@ -2882,6 +2930,132 @@ int crdt_edits_read(crdt_engine* e, uint64_t i, crdt_edit* edits, void* ins_unit
 }
 
 int crdt_last_edits_ms(crdt_engine* e, double* ms) { return job_ms(e, &crdt_engine::ed, ms); }
+
+int crdt_rebase_async(crdt_engine* e, int src) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  if (src != CRDT_REBASE_FROM_DIFF && src != CRDT_REBASE_FROM_EDITS) {
+    g_last_error = "rebase: src is CRDT_REBASE_FROM_DIFF or CRDT_REBASE_FROM_EDITS";
+    return CRDT_E_ARG;
+  }
+  if (!(src == CRDT_REBASE_FROM_DIFF ? e->diff.valid : e->ed.valid)) {
+    g_last_error = "rebase: the source has no result";
+    return CRDT_E_ARG;
+  }
+  return oom_as_nomem([&] { return e->run_rebase((u32)src); });
+}
+
+// the map exists and has a table of this kind
+static int rb_query_ok(crdt_engine* e, int kind) {
+  if (!e->rb.valid) {
+    g_last_error = "rebase: no rebase map";
+    return CRDT_E_ARG;
+  }
+  if (kind != CRDT_REBASE_CHARS && kind != CRDT_REBASE_UNITS) {
+    g_last_error = "rebase: kind is CRDT_REBASE_CHARS or CRDT_REBASE_UNITS";
+    return CRDT_E_ARG;
+  }
+  if (kind == CRDT_REBASE_UNITS && e->rb_src != RB_FROM_EDITS) {
+    g_last_error = "rebase: a map built from a diff has no unit table";
+    return CRDT_E_ARG;
+  }
+  return 0;
+}
+static int rb_dir_bias_ok(int dir, int bias) {
+  if (dir != CRDT_REBASE_OLD_TO_NEW && dir != CRDT_REBASE_NEW_TO_OLD) {
+    g_last_error = "rebase: dir is CRDT_REBASE_OLD_TO_NEW or CRDT_REBASE_NEW_TO_OLD";
+    return CRDT_E_ARG;
+  }
+  if (bias != CRDT_BIAS_LEFT && bias != CRDT_BIAS_RIGHT) {
+    g_last_error = "rebase: bias is CRDT_BIAS_LEFT or CRDT_BIAS_RIGHT";
+    return CRDT_E_ARG;
+  }
+  return 0;
+}
+// span count i of the map, or nullptr (with the error text set) when the index has none
+static const RbRes* rb_result(crdt_engine* e, uint64_t i) {
+  if (i >= e->rb.n) return nullptr;
+  const RbRes& x = e->rb.res_h[i];
+  if (x.n_spans == INVALID) {
+    g_last_error = "rebase: the source has no result for this index";
+    return nullptr;
+  }
+  return &x;
+}
+
+int crdt_rebase_counts(crdt_engine* e, uint32_t* n_spans) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = rb_query_ok(e, CRDT_REBASE_CHARS);
+  if (r) return r;
+  r = e->rb.finish();
+  if (r) return r;
+  for (u64 i = 0; i < e->rb.n; i++)
+    if (n_spans) n_spans[i] = e->rb.res_h[i].n_spans;
+  return 0;
+}
+
+int crdt_rebase_read(crdt_engine* e, uint64_t i, int kind, crdt_rebase_span* spans) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = rb_query_ok(e, kind);
+  if (r) return r;
+  r = e->rb.finish();
+  if (r) return r;
+  const RbRes* x = rb_result(e, i);
+  if (!x || (x->n_spans && !spans)) return CRDT_E_ARG;
+  const RbSpan* tab = kind == CRDT_REBASE_CHARS ? e->rb_ch.p : e->rb_un.p;
+  if (x->n_spans) HIPCHK(hipMemcpy(spans, tab + x->off, (u64)x->n_spans * sizeof(RbSpan), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int crdt_last_rebase_ms(crdt_engine* e, double* ms) { return job_ms(e, &crdt_engine::rb, ms); }
+
+int crdt_rebase_dev_async(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* x, int kind, int dir, int bias,
+                          uint32_t* y, uint8_t* hit) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = rb_dir_bias_ok(dir, bias);
+  if (r) return r;
+  r = rb_query_ok(e, kind);
+  if (r) return r;
+  if (!n) return 0;
+  if (!idx || !x || !y) return CRDT_E_ARG;
+  const RbSpan* tab = kind == CRDT_REBASE_CHARS ? e->rb_ch.p : e->rb_un.p;
+  u32 blocks = (u32)std::min<u64>((n + 255) / 256, 8192);
+  if (dir == CRDT_REBASE_OLD_TO_NEW)
+    hipLaunchKernelGGL(k_rebase<RB_OLD_TO_NEW>, dim3(blocks), dim3(256), 0, e->stream, e->rb.res.p, tab, (u32)e->rb.n, n, idx, x, (u32)bias, y, hit);
+  else
+    hipLaunchKernelGGL(k_rebase<RB_NEW_TO_OLD>, dim3(blocks), dim3(256), 0, e->stream, e->rb.res.p, tab, (u32)e->rb.n, n, idx, x, (u32)bias, y, hit);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int crdt_rebase(crdt_engine* e, uint64_t n, const uint32_t* idx, const uint32_t* x, int kind, int dir, int bias, uint32_t* y,
+                uint8_t* hit) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n && (!idx || !x || !y))) return CRDT_E_ARG;
+  int r = rb_dir_bias_ok(dir, bias);
+  if (r) return r;
+  r = rb_query_ok(e, kind);
+  if (r) return r;
+  r = e->rb.finish();
+  if (r) return r;
+  // the host form names only indexes that have a result (checked before anything is written)
+  for (uint64_t q = 0; q < n; q++)
+    if (!rb_result(e, idx[q])) return CRDT_E_ARG;
+  if (!n) return 0;
+  QStage q{e, n};
+  r = q.reserve(4 + 4 + 4 + 1);
+  if (r) return r;
+  u32* d_idx = q.in(idx);
+  u32* d_x = q.in(x);
+  u32* d_y = q.out(y);
+  u8* d_hit = q.out(hit);
+  if (q.err) return q.err;
+  r = crdt_rebase_dev_async(e, n, d_idx, d_x, kind, dir, bias, d_y, hit ? d_hit : nullptr);
+  return r ? r : q.finish();
+}
 
 int crdt_checkout_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* version) {
   if (poisoned(e)) return CRDT_E_NOMEM;
