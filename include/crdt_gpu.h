@@ -615,6 +615,18 @@ int crdt_set_device_intern(crdt_engine* e, int on);
  *     searches per thread; unsorted or mixed chunks are answered per thread. */
 enum { CRDT_QUERY_LDS = 0, CRDT_QUERY_PER_THREAD = 1, CRDT_QUERY_MERGE = 2 };
 int crdt_set_query_kernel(crdt_engine* e, int mode);
+// on != 0 (the default; CRDT_NO_FUSED_PUBLISH=1 in the environment makes it off): a replay launched
+// onto an index that crdt_fit sized for the staged streams (fit, reset, run, publish: the steady
+// loop) has each replay wave publish its own document as it finishes; crdt_publish_async then only
+// publishes the documents no wave did.  Same published index, bit for bit, either way.
+int crdt_set_fused_publish(crdt_engine* e, int on);
+// Test hook: replay launches (crdt_run, crdt_run_async) so far that ran with the fused publish on (launches, may be NULL), and
+// per document (per_doc: n_docs bytes, may be NULL; waits for the stream) whether its current index
+// was written by its replay wave.
+int crdt_fused_publish_stats(crdt_engine* e, uint64_t* launches, uint8_t* per_doc);
+/* The published index's visible-prefix array of one document (crdt_canon_counts entries: visible
+ * items before each canonical span; debugging and tests).  Publishes first if needed. */
+int crdt_debug_vpos(crdt_engine* e, uint32_t doc, uint32_t* vpos);
 // Device bytes the engine holds (per-document pools, staged records, content, text).
 uint64_t crdt_mem_bytes(const crdt_engine* e);
 // Device bytes the engines of this process hold through their own allocations now, and the most

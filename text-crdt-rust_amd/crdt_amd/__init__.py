@@ -246,9 +246,12 @@ def lib():
         if hasattr(L, f):
             getattr(L, f).argtypes = at
     L.crdt_set_share_streams.argtypes = [vp, C.c_int]
-    for f in ("crdt_set_device_intern", "crdt_set_query_kernel"):
+    for f in ("crdt_set_device_intern", "crdt_set_query_kernel", "crdt_set_fused_publish"):
         if hasattr(L, f):  # (older libraries, for A/B runs, lack them)
             getattr(L, f).argtypes = [vp, C.c_int]
+    if hasattr(L, "crdt_fused_publish_stats"):
+        L.crdt_fused_publish_stats.argtypes = [vp, P(u64), P(C.c_uint8)]
+        L.crdt_debug_vpos.argtypes = [vp, u32, P(u32)]
     L.crdt_apply_local_probed.argtypes = [vp, u64, P(u32), P(u64), vp, vp, vp, vp, P(i32)]
     L.crdt_mem_bytes.argtypes = [vp]
     L.crdt_mem_bytes.restype = u64
@@ -361,6 +364,7 @@ EXPORTED_SYMBOLS = [
     "crdt_find_async", "crdt_find_counts", "crdt_find_read", "crdt_find_seek", "crdt_find_seek_dev_async", "crdt_last_find_ms",
     "crdt_edits_async", "crdt_edits_counts", "crdt_edits_read", "crdt_last_edits_ms",
     "crdt_rebase_async", "crdt_rebase_counts", "crdt_rebase_read", "crdt_rebase", "crdt_rebase_dev_async", "crdt_last_rebase_ms",
+    "crdt_set_fused_publish", "crdt_fused_publish_stats", "crdt_debug_vpos",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -564,6 +568,24 @@ class Engine:
     def device_intern(self, on: bool = True):
         """stage_remote_replicated interns every document's authors with k_intern (same ids)"""
         _check(self.L.crdt_set_device_intern(self.h, int(on)), "device_intern")
+
+    def fused_publish(self, on: bool = True):
+        """replay waves publish their own documents on a fitted index (default on; same index)"""
+        _check(self.L.crdt_set_fused_publish(self.h, int(on)), "fused_publish")
+
+    def fused_publish_stats(self):
+        """(k_replay launches with the fused publish on, per document: the current index was written
+        by its replay wave)"""
+        n = C.c_uint64()
+        per = np.zeros(self.n_docs, np.uint8)
+        _check(self.L.crdt_fused_publish_stats(self.h, C.byref(n), _p(per, C.c_uint8)), "fused_publish_stats")
+        return n.value, per.astype(bool)
+
+    def debug_vpos(self, doc: int) -> np.ndarray:
+        """visible items before each canonical span of the document's published index"""
+        out = np.zeros(max(int(self.canon_counts()[doc]), 1), np.uint32)
+        _check(self.L.crdt_debug_vpos(self.h, doc, _p(out)), "debug_vpos")
+        return out[: int(self.canon_counts()[doc])]
 
     def mem_bytes(self) -> int:
         """device bytes held by the per-document pools + staged records"""

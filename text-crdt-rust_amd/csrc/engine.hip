@@ -364,6 +364,22 @@ struct crdt_engine {
   // the small documents' order -> span index is built in LDS (k_pub_index) when their bitmap has
   // at most PUBX_MAX_WORDS words; pubx_words = the largest such bitmap (the launch's LDS size)
   u32 pubx_words = 0;
+  // fused publish: a replay launch on a fitted index (pub_sized and pub_fitted: the index holds
+  // exactly what the staged streams' replay publishes) has every k_replay wave publish its own
+  // document and stamp it with the launch's id; k_publish then skips the documents so stamped.
+  // state_id is bumped by whatever changes the documents' state or re-sizes the index (replay
+  // launches, reset, reseed, staging, relayout, size_pub), so a stamp never outlives the state
+  // it was made from; it is never 0 (no stamp) or STAMP_BIG (a k_publish_big document).
+  u32* stamp = nullptr;  // [doc] (PubOut::stamp)
+  u64 fused_launches = 0;  // replay launches with the fused publish on (crdt_fused_publish_stats)
+  u32 state_id = 1;
+  bool fused_publish = !(getenv("CRDT_NO_FUSED_PUBLISH") && getenv("CRDT_NO_FUSED_PUBLISH")[0] == '1');  // (A/B switch)
+  void state_changed() {
+    if (++state_id == STAMP_BIG) {  // (wrapped: the stamps are written again by the next size_pub)
+      state_id = 1;
+      pub_sized = pub_fitted = false;
+    }
+  }
   u32* tlen = nullptr;
   u64* tdigest = nullptr;
   bool materialized = false;
@@ -472,6 +488,7 @@ struct crdt_engine {
     o.canon_n = canon_n;
     o.len = len;
     o.digest = digest;
+    o.stamp = stamp;
     return o;
   }
 
@@ -482,7 +499,7 @@ struct crdt_engine {
     pub_big.clear();
     canon_alloc = pub_alloc = 0;
     pub_sized = pub_fitted = false;
-    dfree(st); dfree(segs); dfree(canon_n); dfree(len); dfree(digest); dfree(n_agents_d); dfree(doc_list);
+    dfree(st); dfree(segs); dfree(canon_n); dfree(len); dfree(digest); dfree(stamp); dfree(n_agents_d); dfree(doc_list);
     n_agents_pushed.clear();
     classes.clear();
     dfree(recs);
@@ -524,6 +541,7 @@ struct crdt_engine {
     HIPCHK(dalloc(canon_n, n));
     HIPCHK(dalloc(len, n));
     HIPCHK(dalloc(digest, n));
+    HIPCHK(dalloc(stamp, n));
     HIPCHK(dalloc(n_agents_d, n));
     HIPCHK(dalloc(cbase, n));
     HIPCHK(dalloc(clen, n));
@@ -534,6 +552,7 @@ struct crdt_engine {
     HIPCHK(hipMemsetAsync(cbase, 0xFF, sizeof(u64) * std::max<u64>(n, 1), stream));
     HIPCHK(hipMemsetAsync(clen, 0, sizeof(u64) * std::max<u64>(n, 1), stream));
     HIPCHK(hipMemsetAsync(st, 0, sizeof(DocState) * std::max<u64>(n, 1), stream));
+    HIPCHK(hipMemsetAsync(stamp, 0, 4 * std::max<u64>(n, 1), stream));
     // size every document for an empty stream and initialise it
     for (u64 d = 0; d < n; d++) docs[d].caps = plan_caps(StreamNeeds{}, 0, true, 48);
     r = layout(false);
@@ -700,6 +719,7 @@ struct crdt_engine {
     pub_sized = false;
     published = false;
     materialized = false;
+    state_changed();
     return 0;
   }
 
@@ -743,13 +763,18 @@ struct crdt_engine {
     pub_small.clear();
     pub_big.clear();
     pubx_words = 0;
+    // (the index moved: no stamp holds; the long documents' stamps keep the replay waves off them)
+    state_changed();
+    std::vector<u32> stamps(n_docs, 0u);
     for (u64 d = 0; d < n_docs; d++) {
       u32 nl = st_h[d].n_leaves;
       bool big = nl >= PUB_BIG_MAX || (nl >= PUB_BIG_MIN && n_docs <= PUB_BIG_FEW_DOCS);
       (big ? pub_big : pub_small).push_back((u32)d);
+      if (big) stamps[d] = STAMP_BIG;
       u32 nw = pub_words(seg_h[d].ord_cap);
       if (!big && nw <= PUBX_MAX_WORDS) pubx_words = std::max(pubx_words, nw);
     }
+    HIPCHK(hipMemcpyAsync(stamp, stamps.data(), n_docs * 4, hipMemcpyHostToDevice, stream));
     dfree(pub_list);
     if (!pub_big.empty()) {
       std::vector<u32> all(pub_small);
@@ -854,6 +879,7 @@ struct crdt_engine {
     }
     published = false;
     materialized = false;
+    state_changed();
     return 0;
   }
 
@@ -1078,12 +1104,17 @@ struct crdt_engine {
     HIPCHK(hipStreamSynchronize(stream));
     published = false;
     materialized = false;
+    state_changed();
     return 0;
   }
 
   int launch_replay() {
     if (!n_docs) return 0;
     Pools pv = pools_view(pools);
+    state_changed();  // (this launch's id)
+    // fused publish (above): only onto an index fitted to the staged streams -- a replay that grows
+    // the state is followed by size_pub, which would discard what the waves published
+    const bool fuse = fused_publish && pub_sized && pub_fitted;
     for (const RootClass& c : classes) {  // one launch per root class (usually one)
       LaunchShape sh = launch_shape(c.rcap, c.hr);
       u32 blocks = (u32)((c.n + sh.wpb - 1) / sh.wpb);
@@ -1092,20 +1123,22 @@ struct crdt_engine {
         if (L == 32) hipLaunchKernelGGL(k_replay_hr<32>, dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
         else hipLaunchKernelGGL(k_replay_hr<4>, dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
       } else {  // (one instance per stream shape)
+        ReplayArgs ra{pv, (u32)c.n, sh.wpb, sh.rcap, list, pub_view(), pubx_words, fuse ? state_id : 0u};
         if (L == 32) {
-          if (c.shape == SHAPE_REMOTE) hipLaunchKernelGGL((k_replay<32, SHAPE_REMOTE>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
-          else if (c.shape == SHAPE_GEN) hipLaunchKernelGGL((k_replay<32, SHAPE_GEN>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
-          else if (c.shape == SHAPE_LOCAL) hipLaunchKernelGGL((k_replay<32, SHAPE_LOCAL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
-          else hipLaunchKernelGGL((k_replay<32, SHAPE_ALL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
+          if (c.shape == SHAPE_REMOTE) hipLaunchKernelGGL((k_replay<32, SHAPE_REMOTE>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
+          else if (c.shape == SHAPE_GEN) hipLaunchKernelGGL((k_replay<32, SHAPE_GEN>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
+          else if (c.shape == SHAPE_LOCAL) hipLaunchKernelGGL((k_replay<32, SHAPE_LOCAL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
+          else hipLaunchKernelGGL((k_replay<32, SHAPE_ALL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
         } else {
-          if (c.shape == SHAPE_REMOTE) hipLaunchKernelGGL((k_replay<4, SHAPE_REMOTE>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
-          else if (c.shape == SHAPE_GEN) hipLaunchKernelGGL((k_replay<4, SHAPE_GEN>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
-          else if (c.shape == SHAPE_LOCAL) hipLaunchKernelGGL((k_replay<4, SHAPE_LOCAL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
-          else hipLaunchKernelGGL((k_replay<4, SHAPE_ALL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
+          if (c.shape == SHAPE_REMOTE) hipLaunchKernelGGL((k_replay<4, SHAPE_REMOTE>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
+          else if (c.shape == SHAPE_GEN) hipLaunchKernelGGL((k_replay<4, SHAPE_GEN>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
+          else if (c.shape == SHAPE_LOCAL) hipLaunchKernelGGL((k_replay<4, SHAPE_LOCAL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
+          else hipLaunchKernelGGL((k_replay<4, SHAPE_ALL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
         }
       }
       HIPCHK(hipGetLastError());
     }
+    for (const RootClass& c : classes) if (fuse && !c.hr) { fused_launches++; break; }
     if (!pub_fitted) pub_sized = false;  // the state grows: size the index again before publishing
     published = false;
     materialized = false;
@@ -1124,7 +1157,11 @@ struct crdt_engine {
     if (r) return r;
     for (int iter = 0; iter < 40; iter++) {
       HIPCHK(hipEventRecord(ev[0], stream));
+      // (no fused publish here: size_pub below sizes the index again, which drops every stamp)
+      const bool fused = fused_publish;
+      fused_publish = false;
       r = launch_replay();
+      fused_publish = fused;
       if (r) return r;
       HIPCHK(hipEventRecord(ev[1], stream));
       r = pull_states();
@@ -1247,8 +1284,8 @@ struct crdt_engine {
     if (ns) {
       // documents whose bitmap fits pubx_words get their index from k_pub_index (k_publish skips it)
       u32 xw = pubx_words;
-      if (L == 32) hipLaunchKernelGGL(k_publish<32>, dim3(blocks), dim3(256), 0, stream, pv, ov, ns, (const u32*)pub_list, xw);
-      else hipLaunchKernelGGL(k_publish<4>, dim3(blocks), dim3(256), 0, stream, pv, ov, ns, (const u32*)pub_list, xw);
+      if (L == 32) hipLaunchKernelGGL(k_publish<32>, dim3(blocks), dim3(256), 0, stream, pv, ov, ns, (const u32*)pub_list, xw, state_id);
+      else hipLaunchKernelGGL(k_publish<4>, dim3(blocks), dim3(256), 0, stream, pv, ov, ns, (const u32*)pub_list, xw, state_id);
       HIPCHK(hipGetLastError());
       if (xw) {
         hipLaunchKernelGGL(k_pub_index, dim3(ns), dim3(PUBX_THREADS), pubx_lds_bytes(xw), stream, pv, ov,
@@ -2490,6 +2527,38 @@ int crdt_set_query_kernel(crdt_engine* e, int mode) {
   return 0;
 }
 
+int crdt_set_fused_publish(crdt_engine* e, int on) {
+  if (!e) return CRDT_E_ARG;
+  e->fused_publish = on != 0;
+  return 0;
+}
+
+int crdt_fused_publish_stats(crdt_engine* e, uint64_t* launches, uint8_t* per_doc) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  if (launches) *launches = e->fused_launches;
+  if (per_doc && e->n_docs) {
+    std::vector<u32> st(e->n_docs);
+    HIPCHK(hipMemcpyAsync(st.data(), e->stamp, e->n_docs * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (u64 d = 0; d < e->n_docs; d++) per_doc[d] = st[d] == e->state_id;
+  }
+  return 0;
+}
+
+int crdt_debug_vpos(crdt_engine* e, uint32_t doc, uint32_t* vpos) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || doc >= e->n_docs || !vpos) return CRDT_E_ARG;
+  int r = e->ensure_published();
+  if (r) return r;
+  u32 cn = 0;
+  HIPCHK(hipMemcpyAsync(&cn, e->canon_n + doc, 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (cn) HIPCHK(hipMemcpyAsync(vpos, e->vpos + e->seg_h[doc].canon_base, cn * 4ull, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
 int crdt_set_device_intern(crdt_engine* e, int on) {
   if (!e) return CRDT_E_ARG;
   e->intern_on_device = on != 0;
@@ -2523,6 +2592,7 @@ int crdt_reseed_random_async(crdt_engine* e, uint64_t seed, uint64_t id_base) {
   HIPCHK(hipGetLastError());
   e->published = false;
   e->materialized = false;
+  e->state_changed();
   return 0;
 }
 

@@ -31,7 +31,10 @@ struct PubOut {
   u32* canon_n;   // [doc]
   u32* len;       // [doc]
   u64* digest;    // [doc]
+  u32* stamp;     // [doc]  id of the replay launch whose wave published the document (fused publish:
+                  //        publish_doc from replay_doc), 0 = none, STAMP_BIG = a k_publish_big document
 };
+constexpr u32 STAMP_BIG = 0xFFFFFFFFu;  // (no launch id: the host's counter skips it)
 
 // Order -> canonical span through the published index: r = span starts at or below `order`;
 // the span is sorted[r - 1] if it contains the order (delete orders lie in no span).  Returns
@@ -97,10 +100,28 @@ __global__ __launch_bounds__(256) void k_init(Pools P, u32 n, u32 wpb, u32 rcap)
 // documents in 185 ms where the compiler's own choice (84 VGPRs: 5 waves/SIMD) takes 199 ms and
 // 97 VGPRs (4 waves/SIMD) took 216 ms (scripts/gpu_ab.sh).  What the budget costs is a few spills
 // in cold paths.
-template <int L, bool HR, u32 SH = SHAPE_ALL>
+// k_replay's arguments, one struct: the kernel-argument segment then has this layout, and the
+// fused publish (publish_tail) reads its part from the segment when it runs.  O, xw, pub_id are
+// never read as kernel arguments, so the replay loop carries none of them in registers.
+// pub_id != 0: every wave publishes its document after finish() and stamps it with pub_id, the
+// host's id of this launch (k_publish skips the documents so stamped); 0: no fused publish.
+struct ReplayArgs {
+  Pools P;
+  u32 n, wpb, rcap;
+  const u32* list;
+  PubOut O;
+  u32 xw, pub_id;
+};
+template <int L>
+__device__ __forceinline__ void publish_tail(const DocState* stp);
+
+template <int L, bool HR, u32 SH = SHAPE_ALL, bool FUSE = false>
 __device__ __forceinline__ void replay_doc(Pools P, u32 n, u32 wpb, u32 rcap, const u32* list) {
   u32 d;
   if (!wave_doc(wpb, list, n, d)) return;
+#ifdef CRDT_PROF
+  const u32 life_t0 = (u32)__builtin_amdgcn_s_memrealtime();  // (prof_mode 4: wave lifetimes)
+#endif
   Replayer<WaveGPU<L, HR>, L> r(P, d, wave_with_root<L, HR>(rcap));
   WaveGPU<L, HR>& w = r.w;
   if (r.status() == ST_NEED_CAPACITY) r.p(S_STATUS, (u32)ST_OK);  // resume after growth
@@ -111,6 +132,23 @@ __device__ __forceinline__ void replay_doc(Pools P, u32 n, u32 wpb, u32 rcap, co
   r.begin();
   r.template run<SH>();
   r.finish();
+#ifdef CRDT_PROF
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // (finish()'s stores have left the wave)
+  const u32 life_t1 = (u32)__builtin_amdgcn_s_memrealtime();
+#endif
+  if constexpr (FUSE) publish_tail<L>(r.stp());  // (the document from its state pointer: d need not live through the loop)
+#ifdef CRDT_PROF
+  if (r.prof_mode == 4u) {
+    // over the path counters: start and end (after finish()) on the 100 MHz real-time counter,
+    // HW_ID, and XCC_ID (bits 0-3) with the ticks the fused publish then took above it (<< 4)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    const u32 tail = (u32)__builtin_amdgcn_s_memrealtime() - life_t1;
+    w.st(&P.st[d].prof0, life_t0);
+    w.st(&P.st[d].prof1, life_t1);
+    w.st(&P.st[d].prof2, (u32)__builtin_amdgcn_s_getreg(4 | (31 << 11)));
+    w.st(&P.st[d].prof3, ((u32)__builtin_amdgcn_s_getreg(20 | (31 << 11)) & 15u) | (tail << 4));
+  }
+#endif
 }
 #ifndef CRDT_REPLAY_WAVES
 #define CRDT_REPLAY_WAVES 8  // waves per SIMD the replay's register budget is held to (diagnostic builds vary it)
@@ -121,8 +159,8 @@ __device__ __forceinline__ void replay_doc(Pools P, u32 n, u32 wpb, u32 rcap, co
 #define CRDT_REPLAY_WAVES_GEN CRDT_REPLAY_WAVES  // (the generated-op instance's budget; diagnostic builds vary it)
 #endif
 template <int L, u32 SH>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SH == SHAPE_GEN ? CRDT_REPLAY_WAVES_GEN : CRDT_REPLAY_WAVES))) void k_replay(Pools P, u32 n, u32 wpb, u32 rcap, const u32* list) {
-  replay_doc<L, false, SH>(P, n, wpb, rcap, list);
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SH == SHAPE_GEN ? CRDT_REPLAY_WAVES_GEN : CRDT_REPLAY_WAVES))) void k_replay(ReplayArgs A) {
+  replay_doc<L, false, SH, true>(A.P, A.n, A.wpb, A.rcap, A.list);
 }
 // Documents past the LDS root replay with the two-level root (wave_gpu.h HR).  They are few and
 // long, so this instance is held to 4 waves per SIMD (<= 128 VGPRs: no scratch for its extra
@@ -287,6 +325,10 @@ __device__ __forceinline__ u64 wave_sum64(u64 v) {
 #ifndef PUB_DEPTH
 #define PUB_DEPTH 1  // compaction steps whose leaf loads are in flight at once (compact_range)
 #endif
+#ifndef PUB_TAIL_DEPTH
+#define PUB_TAIL_DEPTH 3  // the same for a replay wave's own publish (publish_tail): the waves of a SIMD end one
+                          // after the other, so a publishing wave has the memory system nearly to itself
+#endif
 #define PUB_BIG_WAVES 16
 #define PUB_BIG_MIN 2048u        // leaves from which a document may publish with a workgroup ...
 #define PUB_BIG_FEW_DOCS 1024u   // ... when the batch has at most this many documents
@@ -317,7 +359,9 @@ struct RangeSum {
 // skip_first: the range's first span continues the previous range's (not written); extra: the
 // signed length the range's last span continues by in later ranges.  !WRITE: fill `sum`.
 // Every written span's first order also goes to corder.
-template <int L, bool WRITE>
+// DEPTH: compaction steps whose leaf loads are in flight at once (PUB_DEPTH for the publish kernels,
+// whose 8 waves per SIMD walk together; PUB_TAIL_DEPTH for a replay wave's own publish).
+template <int L, bool WRITE, int DEPTH = PUB_DEPTH>
 __device__ __forceinline__ void compact_range(const Pools& P, const DocSeg& seg, u32 ng, u32 a, u32 b, Span* canon,
                                               u32* vpos, u32* corder, u32 ccap, u32& out, u32& vis, u32 skip_first,
                                               i32 extra, RangeSum& sum) {
@@ -361,31 +405,32 @@ __device__ __forceinline__ void compact_range(const Pools& P, const DocSeg& seg,
       u32 leaf = shfl(mydl, li < iend ? li : 0u);
       return *(const uint4*)(leaves + (u64)leaf * L + (l & (u32)(L - 1)));
     };
-    // PUB_DEPTH steps of loads in flight (Little's law: one wave's 1 KiB per step is too little to
+    // DEPTH steps of loads in flight (Little's law: one wave's 1 KiB per step is too little to
     // cover HBM latency at 8 waves per SIMD)
     uint4 vn = ld(i0);
-#if PUB_DEPTH >= 2
-    uint4 vn2 = i0 + PER < iend ? ld(i0 + PER) : uint4{0, 0, 0, 0};
-#endif
-#if PUB_DEPTH >= 3
-    uint4 vn3 = i0 + 2u * PER < iend ? ld(i0 + 2u * PER) : uint4{0, 0, 0, 0};
-#endif
+    uint4 vn2{0, 0, 0, 0}, vn3{0, 0, 0, 0};
+    if constexpr (DEPTH >= 2) {
+      if (i0 + PER < iend) vn2 = ld(i0 + PER);
+    }
+    if constexpr (DEPTH >= 3) {
+      if (i0 + 2u * PER < iend) vn3 = ld(i0 + 2u * PER);
+    }
     for (u32 i = i0; i < iend; i += PER) {
       uint4 v = vn;
       {  // lanes of leaves past the group's range: empty
         bool in = i + sub < iend;
         v = uint4{in ? v.x : 0u, in ? v.y : 0u, in ? v.z : 0u, in ? v.w : 0u};
       }
-#if PUB_DEPTH >= 3
-      vn = vn2;
-      vn2 = vn3;
-      if (i + 3u * PER < iend) vn3 = ld(i + 3u * PER);
-#elif PUB_DEPTH >= 2
-      vn = vn2;
-      if (i + 2u * PER < iend) vn2 = ld(i + 2u * PER);
-#else
-      if (i + PER < iend) vn = ld(i + PER);
-#endif
+      if constexpr (DEPTH >= 3) {
+        vn = vn2;
+        vn2 = vn3;
+        if (i + 3u * PER < iend) vn3 = ld(i + 3u * PER);
+      } else if constexpr (DEPTH >= 2) {
+        vn = vn2;
+        if (i + 2u * PER < iend) vn2 = ld(i + 2u * PER);
+      } else {
+        if (i + PER < iend) vn = ld(i + PER);
+      }
       u64 VM = ballot(v.w != 0u);
       u32 nn = (u32)__popcll(VM);
       if (PER > 1) {
@@ -609,30 +654,27 @@ __device__ __forceinline__ u64 digest_counts(const DocState& s, u32 out) {
   return counts ^ elem_hash(9, 0, ((u64)s.n_dd << 32) | s.n_txn, ((u64)s.n_fr << 32) | s.n_par);
 }
 
+// One wave publishes document d (k_publish; publish_tail: the wave that replayed it).
 // xw: documents whose bitmap has at most xw words get their order -> span index from k_pub_index
 // (launched next); the others build it here.
-// (8 waves per SIMD need <= 80 SGPRs: unconstrained, the compiler took 102, i.e. 6 waves per SIMD and
-// 8,192 documents in 1.33 rounds)
-template <int L>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_publish(Pools P, PubOut O, u32 n, const u32* list, u32 xw) {
-  u32 d;
-  if (!wave_doc(WAVES_PER_BLOCK, list, n, d)) return;
+template <int L, int DEPTH = PUB_DEPTH>
+__device__ __forceinline__ void publish_doc(const Pools& P, const PubOut& O, u32 d, u32 xw, u32 stamp) {
   WaveGPU<L> w;
   DocState s = w.ldT(P.st + d);
   DocSeg seg = w.ld_seg(P.seg + d);
   u32 l = lane_id();
   if ((s.status != ST_OK && s.status != ST_NEED_CAPACITY) || s.next_order >= seg.ord_cap) {
-    if (l == 0) { O.canon_n[d] = 0; O.len[d] = s.len; O.digest[d] = 0; }
+    if (l == 0) { O.canon_n[d] = 0; O.len[d] = s.len; O.digest[d] = 0; O.stamp[d] = stamp; }
     return;
   }
   Span* canon = O.canon + seg.canon_base;
   u32* vpos = O.vpos + seg.canon_base;
   u32 out = 0, vis = 0;
   RangeSum sum{};
-  compact_range<L, true>(P, seg, s.ng, 0u, s.n_leaves, canon, vpos, O.corder + seg.canon_base, seg.canon_cap,
-                         out, vis, 0u, 0, sum);
+  compact_range<L, true, DEPTH>(P, seg, s.ng, 0u, s.n_leaves, canon, vpos, O.corder + seg.canon_base, seg.canon_cap,
+                                out, vis, 0u, 0, sum);
   if (out > seg.canon_cap) {  // canonical spans beyond the planned capacity: report, never write past it
-    if (l == 0) { O.canon_n[d] = 0; O.len[d] = s.len; O.digest[d] = 0; }
+    if (l == 0) { O.canon_n[d] = 0; O.len[d] = s.len; O.digest[d] = 0; O.stamp[d] = stamp; }
     return;
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -641,7 +683,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
     O.canon_n[d] = out;
     O.len[d] = s.len;
     O.digest[d] = DIGEST_PENDING;  // (k_digest computes it on request)
+    O.stamp[d] = stamp;
   }
+}
+// The replay wave's publish of its own document, after finish() (fused publish; replay_doc).  What
+// finish() stored -- the state by lanes, the tables' tails, the root groups -- is read back here by
+// other lanes of the same wave: the fence orders those stores before the loads, as the kernel
+// boundary does for k_publish.  Documents of the k_publish_big list (STAMP_BIG) stay with it.
+// The replay's registers are dead here; so that the tail adds nothing to what the replay loop
+// keeps live (k_replay's 8-waves-per-SIMD budget), it takes its arguments from the kernel-argument
+// segment now (ReplayArgs) -- through a pointer the compiler cannot trace back to the segment, or it
+// would merge these loads with the kernel's own at entry and carry the values through the loop.
+typedef const __attribute__((address_space(4))) u32* karg_u32;
+template <class T>
+__device__ __forceinline__ T ld_karg(karg_u32 kp, size_t off) {
+  static_assert(sizeof(T) % 4 == 0, "dwords");
+  T t;
+  u32* o = (u32*)&t;
+#pragma unroll
+  for (u32 k = 0; k < sizeof(T) / 4; k++) o[k] = kp[off / 4 + k];
+  return t;
+}
+template <int L>
+__device__ __forceinline__ void publish_tail(const DocState* stp) {
+  karg_u32 kp = (karg_u32)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("; publish_tail: kernel-argument segment pointer" : "+s"(kp));
+  const u32 pub_id = ld_karg<u32>(kp, offsetof(ReplayArgs, pub_id));
+  if (!pub_id) return;
+  const Pools P = ld_karg<Pools>(kp, offsetof(ReplayArgs, P));
+  const PubOut O = ld_karg<PubOut>(kp, offsetof(ReplayArgs, O));
+  const u32 d = uni((u32)(stp - P.st));
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  if (uni(O.stamp[d]) == STAMP_BIG) return;
+  publish_doc<L, PUB_TAIL_DEPTH>(P, O, d, ld_karg<u32>(kp, offsetof(ReplayArgs, xw)), pub_id);
+}
+
+// pub_id: the host's id of the last replay launch; a document its replay wave published
+// (stamp == pub_id) is current, the wave returns at once.
+// (8 waves per SIMD need <= 80 SGPRs: unconstrained, the compiler took 102, i.e. 6 waves per SIMD and
+// 8,192 documents in 1.33 rounds)
+template <int L>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_publish(Pools P, PubOut O, u32 n, const u32* list, u32 xw, u32 pub_id) {
+  u32 d;
+  if (!wave_doc(WAVES_PER_BLOCK, list, n, d)) return;
+  if (uni(O.stamp[d]) == pub_id) return;
+  publish_doc<L>(P, O, d, xw, 0u);
 }
 
 // Long documents: one workgroup of PUB_BIG_WAVES waves per listed document.
@@ -1279,11 +1365,13 @@ __global__ void k_pos_to_loc(Pools P, PubOut O, u32 n_docs, u64 nq, const u32* d
           u32 mid = (lo + hi) >> 1;
           if (vp[mid] <= p) lo = mid + 1; else hi = mid;
         }
-        u32 k = lo - 1;
-        u32 order = cn[k].order + (p - vp[k]);
-        const CwoRun* cw = P.cwo + seg.cwo_base;
-        i32 r = find_run(cw, P.st[d].n_cwo, order);
-        if (r >= 0) { a = (u16)cw[r].agent; sq = cw[r].seq + (order - cw[r].key); }
+        if (lo) {  // (no span: a document publish refused has len > 0 and canon_n 0 -- no answer, no vp[-1])
+          u32 k = lo - 1;
+          u32 order = cn[k].order + (p - vp[k]);
+          const CwoRun* cw = P.cwo + seg.cwo_base;
+          i32 r = find_run(cw, P.st[d].n_cwo, order);
+          if (r >= 0) { a = (u16)cw[r].agent; sq = cw[r].seq + (order - cw[r].key); }
+        }
       }
     }
     agent[q] = a;
@@ -1329,7 +1417,7 @@ __global__ __launch_bounds__(QBLK_T) void k_pos_to_loc_blk(Pools P, PubOut O, u3
     cn = O.canon_n[d0];
     if ((stt == ST_OK || stt == ST_NEED_CAPACITY) && cn <= QBLK_MAX) {
       seg = P.seg[d0];
-      dlen = O.len[d0];
+      dlen = cn ? O.len[d0] : 0u;  // (a document publish refused: no span, no answer)
       ncwo = P.st[d0].n_cwo;
       const u32* vp = O.vpos + seg.canon_base;
       for (u32 i0 = 0; i0 < cn; i0 += QBLK_T * 16u) {  // 16 loads per thread in flight per step
@@ -1364,11 +1452,13 @@ __global__ __launch_bounds__(QBLK_T) void k_pos_to_loc_blk(Pools P, PubOut O, u3
             u32 mid = (lo + hi) >> 1;
             if (vp[mid] <= p) lo = mid + 1; else hi = mid;
           }
-          u32 k = lo - 1;
-          u32 order = O.canon[sg.canon_base + k].order + (p - vp[k]);
-          const CwoRun* cw = P.cwo + sg.cwo_base;
-          i32 r = find_run(cw, P.st[d].n_cwo, order);
-          if (r >= 0) { a = (u16)cw[r].agent; sq = cw[r].seq + (order - cw[r].key); }
+          if (lo) {  // (as k_pos_to_loc: a document publish refused has no span to answer from)
+            u32 k = lo - 1;
+            u32 order = O.canon[sg.canon_base + k].order + (p - vp[k]);
+            const CwoRun* cw = P.cwo + sg.cwo_base;
+            i32 r = find_run(cw, P.st[d].n_cwo, order);
+            if (r >= 0) { a = (u16)cw[r].agent; sq = cw[r].seq + (order - cw[r].key); }
+          }
         }
       }
       agent[q] = a;
@@ -2061,11 +2151,13 @@ __global__ __launch_bounds__(QM_T) void k_pos_to_loc_merge(Pools P, PubOut O, u3
             u32 mid = (lo + hi) >> 1;
             if (vp[mid] <= p) lo = mid + 1; else hi = mid;
           }
-          u32 k = lo - 1;
-          u32 order = O.corder[sg.canon_base + k] + (p - vp[k]);
-          const CwoRun* cw = P.cwo + sg.cwo_base;
-          i32 r = find_run(cw, P.st[d].n_cwo, order);
-          if (r >= 0) { a = (u16)cw[r].agent; sq = cw[r].seq + (order - cw[r].key); }
+          if (lo) {  // (as k_pos_to_loc: a document publish refused has no span to answer from)
+            u32 k = lo - 1;
+            u32 order = O.corder[sg.canon_base + k] + (p - vp[k]);
+            const CwoRun* cw = P.cwo + sg.cwo_base;
+            i32 r = find_run(cw, P.st[d].n_cwo, order);
+            if (r >= 0) { a = (u16)cw[r].agent; sq = cw[r].seq + (order - cw[r].key); }
+          }
         }
       }
       agent[q] = a;

@@ -127,7 +127,8 @@ struct Replayer {
   }
 #ifdef CRDT_PROF
   u32 prof_cat = 0;  // diagnostic: which fast path ran (0 typing, 2 delete, 3 insert)
-  u32 prof_mode = 0; // document d % 4: 0 cycles, 1 calls, 2 txns per path, 3 detail (below)
+  u32 prof_mode = 0; // document d % 4: 0 cycles, 1 calls, 2 txns per path, 3 detail (below);
+                     // -DCRDT_PROF_MODE=4, every document: the wave's start, end and placement
   u32 prof_gen = 0;  // generated ops (config 4): detail = gen / fast path / cursor / leaf switch
   u32 prof_cur = 0, prof_sw = 0;  // cycles in cursor_at_content_pos and in its leaf switches
   u64 prof_t2 = 0;    // (compact local loop detail)
@@ -181,7 +182,11 @@ struct Replayer {
 
   CRDT_HD Replayer(const Pools& P, u32 d, const W& w0 = W()) : w(w0) {
 #ifdef CRDT_PROF
+#ifdef CRDT_PROF_MODE  // one view for every document (4: wave lifetimes, kernels.h replay_doc)
+    prof_mode = CRDT_PROF_MODE;
+#else
     prof_mode = d & 3u;
+#endif
 #endif
     DocSeg sg = w.ld_seg(P.seg + d);
     w.bind_root(P, sg);  // (the two-level root's HBM rows, for documents past the LDS root)
