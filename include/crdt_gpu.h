@@ -627,6 +627,11 @@ int crdt_fused_publish_stats(crdt_engine* e, uint64_t* launches, uint8_t* per_do
 /* The published index's visible-prefix array of one document (crdt_canon_counts entries: visible
  * items before each canonical span; debugging and tests).  Publishes first if needed. */
 int crdt_debug_vpos(crdt_engine* e, uint32_t doc, uint32_t* vpos);
+/* What the host planned for each document at the last index sizing: plan[d] = 0 k_publish + k_pub_index,
+   1 k_publish building the index in its own wave (bitmap words > the launch's k_pub_index size),
+   2 k_publish_big; words[d] = pub_words(ord_cap).  Either pointer may be null (n_docs entries
+   otherwise; debugging and tests).  Publishes first if needed; host state only. */
+int crdt_debug_publish_plan(crdt_engine* e, uint8_t* plan, uint32_t* words);
 // Device bytes the engine holds (per-document pools, staged records, content, text).
 uint64_t crdt_mem_bytes(const crdt_engine* e);
 // Device bytes the engines of this process hold through their own allocations now, and the most

@@ -21,7 +21,7 @@ from test_gpu_edge import _wire_of_local  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAYOUTS = {32: (32, 16), 4: (4, 8)}
 MICRO = ["base", "bs10", "bs200", "del1", "fd200", "jump1", "jump10", "typing"]
-PUB_BIG_MIN = 2048  # kernels.h: leaves from which a document of a small batch publishes with a workgroup
+from kernel_consts import PUB_BIG_MIN  # noqa: E402  (kernels.h: leaves from which a document of a small batch publishes with a workgroup)
 N_QUERIES = 300
 
 

@@ -252,6 +252,8 @@ def lib():
     if hasattr(L, "crdt_fused_publish_stats"):
         L.crdt_fused_publish_stats.argtypes = [vp, P(u64), P(C.c_uint8)]
         L.crdt_debug_vpos.argtypes = [vp, u32, P(u32)]
+    if hasattr(L, "crdt_debug_publish_plan"):
+        L.crdt_debug_publish_plan.argtypes = [vp, P(C.c_uint8), P(u32)]
     L.crdt_apply_local_probed.argtypes = [vp, u64, P(u32), P(u64), vp, vp, vp, vp, P(i32)]
     L.crdt_mem_bytes.argtypes = [vp]
     L.crdt_mem_bytes.restype = u64
@@ -364,7 +366,7 @@ EXPORTED_SYMBOLS = [
     "crdt_find_async", "crdt_find_counts", "crdt_find_read", "crdt_find_seek", "crdt_find_seek_dev_async", "crdt_last_find_ms",
     "crdt_edits_async", "crdt_edits_counts", "crdt_edits_read", "crdt_last_edits_ms",
     "crdt_rebase_async", "crdt_rebase_counts", "crdt_rebase_read", "crdt_rebase", "crdt_rebase_dev_async", "crdt_last_rebase_ms",
-    "crdt_set_fused_publish", "crdt_fused_publish_stats", "crdt_debug_vpos",
+    "crdt_set_fused_publish", "crdt_fused_publish_stats", "crdt_debug_vpos", "crdt_debug_publish_plan",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -586,6 +588,15 @@ class Engine:
         out = np.zeros(max(int(self.canon_counts()[doc]), 1), np.uint32)
         _check(self.L.crdt_debug_vpos(self.h, doc, _p(out)), "debug_vpos")
         return out[: int(self.canon_counts()[doc])]
+
+    def publish_plan(self):
+        """(plan, words) per document, as the host planned them at the last index sizing: plan 0 =
+        k_publish + k_pub_index, 1 = k_publish building the index in its own wave, 2 =
+        k_publish_big; words = the document's span-start bitmap words (pub_words(ord_cap))"""
+        plan = np.zeros(self.n_docs, np.uint8)
+        words = np.zeros(self.n_docs, np.uint32)
+        _check(self.L.crdt_debug_publish_plan(self.h, _p(plan, C.c_uint8), _p(words)), "debug_publish_plan")
+        return plan, words
 
     def mem_bytes(self) -> int:
         """device bytes held by the per-document pools + staged records"""

@@ -2559,6 +2559,22 @@ int crdt_debug_vpos(crdt_engine* e, uint32_t doc, uint32_t* vpos) {
   return 0;
 }
 
+int crdt_debug_publish_plan(crdt_engine* e, uint8_t* plan, uint32_t* words) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  int r = e->ensure_published();
+  if (r) return r;
+  // size_pub's decisions: the k_publish_big list, and the k_pub_index launch's bitmap size
+  for (u64 d = 0; d < e->n_docs; d++) {
+    u32 nw = pub_words(e->seg_h[d].ord_cap);
+    if (plan) plan[d] = nw > e->pubx_words ? 1 : 0;
+    if (words) words[d] = nw;
+  }
+  if (plan)
+    for (u32 d : e->pub_big) plan[d] = 2;
+  return 0;
+}
+
 int crdt_set_device_intern(crdt_engine* e, int on) {
   if (!e) return CRDT_E_ARG;
   e->intern_on_device = on != 0;
