@@ -624,6 +624,29 @@ int crdt_set_fused_publish(crdt_engine* e, int on);
 // per document (per_doc: n_docs bytes, may be NULL; waits for the stream) whether its current index
 // was written by its replay wave.
 int crdt_fused_publish_stats(crdt_engine* e, uint64_t* launches, uint8_t* per_doc);
+/* Progress balance of the replay's waves.  The waves of one SIMD start together, but its issue
+ * arbiter favours the oldest, so equal documents end one after the other and the last replay alone.
+ * With the balance on, every replay wave sets its own issue priority about once per 64 records,
+ * by one of two policies.  Scheduling only: the same state, bit for bit.
+ *   rotation: the four priority levels rotate over the SIMD's wave slots in 82 us time slices, so
+ *     no wave stays the arbiter's favourite (equal documents then end together; no memory traffic);
+ *   board: from the records the wave has left against the other waves resident on its SIMD (most
+ *     left = highest priority), through a 1 MiB board the engine owns: also evens out unequal
+ *     documents, but gains less on equal ones.
+ *   CRDT_BALANCE_AUTO (default): the rotation for a replay launch whose waves are all resident at
+ *     once (documents <= 32 x the device's compute units, fewer where the LDS roots limit
+ *     residency), nothing for launches that run in several rounds;
+ *   CRDT_BALANCE_OFF: never; CRDT_BALANCE_ON / CRDT_BALANCE_ROTATE: the board / the rotation on
+ *     every launch (CRDT_REPLAY_BALANCE=0 / 1 / 3 in the environment sets the engine's initial mode).
+ * Documents past the LDS root (the two-level root's kernel) are never balanced. */
+enum { CRDT_BALANCE_OFF = 0, CRDT_BALANCE_ON = 1, CRDT_BALANCE_AUTO = 2, CRDT_BALANCE_ROTATE = 3 };
+int crdt_set_replay_balance(crdt_engine* e, int mode);
+/* Test hook: the board after the stream has drained (board: CRDT_BALANCE_BOARD_WORDS words, 16 slots
+ * per SIMD row, slot = launch stamp << 24 | records left; may be NULL), the stamp of the last replay
+ * launch (1..255) and the policy it ran with (0 none, 1 the board, 2 rotation).  After a launch no
+ * slot carries a non-zero "records left". */
+#define CRDT_BALANCE_BOARD_WORDS (16384u * 16u)
+int crdt_debug_balance_board(crdt_engine* e, uint32_t* board, uint32_t* stamp, int* policy);
 /* The published index's visible-prefix array of one document (crdt_canon_counts entries: visible
  * items before each canonical span; debugging and tests).  Publishes first if needed. */
 int crdt_debug_vpos(crdt_engine* e, uint32_t doc, uint32_t* vpos);

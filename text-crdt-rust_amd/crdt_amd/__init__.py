@@ -254,6 +254,9 @@ def lib():
         L.crdt_debug_vpos.argtypes = [vp, u32, P(u32)]
     if hasattr(L, "crdt_debug_publish_plan"):
         L.crdt_debug_publish_plan.argtypes = [vp, P(C.c_uint8), P(u32)]
+    if hasattr(L, "crdt_set_replay_balance"):
+        L.crdt_set_replay_balance.argtypes = [vp, C.c_int]
+        L.crdt_debug_balance_board.argtypes = [vp, P(u32), P(u32), P(C.c_int)]
     L.crdt_apply_local_probed.argtypes = [vp, u64, P(u32), P(u64), vp, vp, vp, vp, P(i32)]
     L.crdt_mem_bytes.argtypes = [vp]
     L.crdt_mem_bytes.restype = u64
@@ -367,6 +370,7 @@ EXPORTED_SYMBOLS = [
     "crdt_edits_async", "crdt_edits_counts", "crdt_edits_read", "crdt_last_edits_ms",
     "crdt_rebase_async", "crdt_rebase_counts", "crdt_rebase_read", "crdt_rebase", "crdt_rebase_dev_async", "crdt_last_rebase_ms",
     "crdt_set_fused_publish", "crdt_fused_publish_stats", "crdt_debug_vpos", "crdt_debug_publish_plan",
+    "crdt_set_replay_balance", "crdt_debug_balance_board",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -582,6 +586,22 @@ class Engine:
         per = np.zeros(self.n_docs, np.uint8)
         _check(self.L.crdt_fused_publish_stats(self.h, C.byref(n), _p(per, C.c_uint8)), "fused_publish_stats")
         return n.value, per.astype(bool)
+
+    BALANCE_MODES = {"off": 0, "on": 1, "auto": 2, "rotate": 3}
+
+    def replay_balance(self, mode="auto"):
+        """replay waves set their own issue priority as they go ("auto", the default: the rotation
+        policy on launches whose waves are all resident at once; "off": never; "on" / "rotate": the
+        progress board / the rotation on every launch); same state either way"""
+        _check(self.L.crdt_set_replay_balance(self.h, int(self.BALANCE_MODES.get(mode, mode))), "replay_balance")
+
+    def balance_board(self):
+        """(board [16384, 16] u32: per SIMD row and wave slot, launch stamp << 24 | records left;
+        the last replay launch's stamp; the policy it ran with: 0 none, 1 the board, 2 rotation)"""
+        board = np.zeros((16384, 16), np.uint32)
+        stamp, policy = C.c_uint32(), C.c_int()
+        _check(self.L.crdt_debug_balance_board(self.h, _p(board), C.byref(stamp), C.byref(policy)), "debug_balance_board")
+        return board, stamp.value, policy.value
 
     def debug_vpos(self, doc: int) -> np.ndarray:
         """visible items before each canonical span of the document's published index"""

@@ -374,6 +374,29 @@ struct crdt_engine {
   u64 fused_launches = 0;  // replay launches with the fused publish on (crdt_fused_publish_stats)
   u32 state_id = 1;
   bool fused_publish = !(getenv("CRDT_NO_FUSED_PUBLISH") && getenv("CRDT_NO_FUSED_PUBLISH")[0] == '1');  // (A/B switch)
+  // progress balance of k_replay's waves (kernels.h balance_board_tick).  The board lives with the
+  // engine (crdt_engine_create); a launch's stamp is its state_id folded to 1..255.  Automatic mode
+  // balances the launches whose waves are all resident at once (one round: the waves start together
+  // and the arbiter's age order is what spreads their ends), with the rotation, the faster of the
+  // two policies there; a multi-round launch refills its slots and is left alone.
+  // CRDT_REPLAY_BALANCE=0|1 in the environment forces it off / on (A/B switch; 1: the board, 3: the
+  // rotation, on every launch).
+  u32* bal_board = nullptr;
+  int replay_balance = getenv("CRDT_REPLAY_BALANCE") && getenv("CRDT_REPLAY_BALANCE")[0] >= '0' && getenv("CRDT_REPLAY_BALANCE")[0] <= '3'
+                           ? getenv("CRDT_REPLAY_BALANCE")[0] - '0' : CRDT_BALANCE_AUTO;
+  u32 n_cus = 0;
+  u32 bal_last_stamp = 0, bal_last_mode = BAL_OFF;  // of the last k_replay launch (crdt_debug_balance_board)
+  u32 balance_mode(const RootClass& c, const LaunchShape& sh) const {
+    if (replay_balance == CRDT_BALANCE_OFF) return BAL_OFF;
+    if (replay_balance == CRDT_BALANCE_ROTATE) return BAL_ROTATE;
+    if (replay_balance == CRDT_BALANCE_ON) return BAL_BOARD;
+    // waves resident per CU: the register budget's 8 per SIMD (kernels.h k_replay), or what the
+    // workgroups' LDS roots leave room for (160 KiB per CU)
+    const u64 by_regs = 4ull * (c.shape == SHAPE_GEN ? CRDT_REPLAY_WAVES_GEN : CRDT_REPLAY_WAVES);
+    const u64 by_lds = (163840ull / std::max<size_t>(sh.lds, 1)) * sh.wpb;
+    // (the rotation: on 8,192 equal documents it gains 10 ms of 73.5 where the board gains 2.3)
+    return c.n <= std::min(by_regs, by_lds) * n_cus ? BAL_ROTATE : BAL_OFF;
+  }
   void state_changed() {
     if (++state_id == STAMP_BIG) {  // (wrapped: the stamps are written again by the next size_pub)
       state_id = 1;
@@ -1112,6 +1135,8 @@ struct crdt_engine {
     if (!n_docs) return 0;
     Pools pv = pools_view(pools);
     state_changed();  // (this launch's id)
+    bal_last_stamp = state_id % 255u + 1u;
+    bal_last_mode = BAL_OFF;
     // fused publish (above): only onto an index fitted to the staged streams -- a replay that grows
     // the state is followed by size_pub, which would discard what the waves published
     const bool fuse = fused_publish && pub_sized && pub_fitted;
@@ -1123,7 +1148,10 @@ struct crdt_engine {
         if (L == 32) hipLaunchKernelGGL(k_replay_hr<32>, dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
         else hipLaunchKernelGGL(k_replay_hr<4>, dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, pv, (u32)c.n, sh.wpb, sh.rcap, list);
       } else {  // (one instance per stream shape)
-        ReplayArgs ra{pv, (u32)c.n, sh.wpb, sh.rcap, list, pub_view(), pubx_words, fuse ? state_id : 0u};
+        const u32 bal = balance_mode(c, sh);
+        bal_last_mode = std::max(bal_last_mode, bal);
+        ReplayArgs ra{pv, (u32)c.n, sh.wpb, sh.rcap, list, pub_view(), pubx_words, fuse ? state_id : 0u,
+                      bal_board, bal_last_stamp, bal};
         if (L == 32) {
           if (c.shape == SHAPE_REMOTE) hipLaunchKernelGGL((k_replay<32, SHAPE_REMOTE>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
           else if (c.shape == SHAPE_GEN) hipLaunchKernelGGL((k_replay<32, SHAPE_GEN>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
@@ -2060,6 +2088,10 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
   bool ok = hipSetDevice(e->device) == hipSuccess && hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) == hipSuccess;
   for (auto& x : e->ev) ok = ok && hipEventCreate(&x) == hipSuccess;
   e->each_job([&](auto& j) { ok = ok && j.create(e->device, e->stream) == 0; });
+  // the progress board of k_replay's waves: 1 MiB for the engine's life, outside the documents' pools
+  e->n_cus = (u32)prop.multiProcessorCount;
+  ok = ok && hipMalloc((void**)&e->bal_board, (size_t)BAL_ROWS * BAL_SLOTS * 4) == hipSuccess &&
+       hipMemsetAsync(e->bal_board, 0, (size_t)BAL_ROWS * BAL_SLOTS * 4, e->stream) == hipSuccess;
   if (!ok) {
     crdt_engine_destroy(e);
     return CRDT_E_DEVICE;
@@ -2091,6 +2123,7 @@ void crdt_engine_destroy(crdt_engine* e) {
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   e->release();
+  if (e->bal_board) (void)hipFree(e->bal_board);
   for (auto& x : e->ev)
     if (x) (void)hipEventDestroy(x);
   e->each_job([](auto& j) { j.destroy(); });
@@ -2530,6 +2563,24 @@ int crdt_set_query_kernel(crdt_engine* e, int mode) {
 int crdt_set_fused_publish(crdt_engine* e, int on) {
   if (!e) return CRDT_E_ARG;
   e->fused_publish = on != 0;
+  return 0;
+}
+
+int crdt_set_replay_balance(crdt_engine* e, int mode) {
+  if (!e || mode < CRDT_BALANCE_OFF || mode > CRDT_BALANCE_ROTATE) return CRDT_E_ARG;
+  e->replay_balance = mode;
+  return 0;
+}
+
+int crdt_debug_balance_board(crdt_engine* e, uint32_t* board, uint32_t* stamp, int* policy) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  if (stamp) *stamp = e->bal_last_stamp;
+  if (policy) *policy = (int)e->bal_last_mode;
+  if (board) {
+    HIPCHK(hipMemcpyAsync(board, e->bal_board, (size_t)BAL_ROWS * BAL_SLOTS * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
   return 0;
 }
 

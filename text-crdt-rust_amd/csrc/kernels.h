@@ -105,15 +105,20 @@ __global__ __launch_bounds__(256) void k_init(Pools P, u32 n, u32 wpb, u32 rcap)
 // never read as kernel arguments, so the replay loop carries none of them in registers.
 // pub_id != 0: every wave publishes its document after finish() and stamps it with pub_id, the
 // host's id of this launch (k_publish skips the documents so stamped); 0: no fused publish.
+// bal_*: the progress balance (balance_board_tick below), read from the segment at every tick.
 struct ReplayArgs {
   Pools P;
   u32 n, wpb, rcap;
   const u32* list;
   PubOut O;
   u32 xw, pub_id;
+  u32* bal_board;  // [BAL_ROWS][BAL_SLOTS]
+  u32 bal_stamp;   // this launch's stamp, 1..255
+  u32 bal_mode;    // BAL_*
 };
 template <int L>
 __device__ __forceinline__ void publish_tail(const DocState* stp);
+__device__ __forceinline__ void balance_done();
 
 template <int L, bool HR, u32 SH = SHAPE_ALL, bool FUSE = false>
 __device__ __forceinline__ void replay_doc(Pools P, u32 n, u32 wpb, u32 rcap, const u32* list) {
@@ -127,6 +132,7 @@ __device__ __forceinline__ void replay_doc(Pools P, u32 n, u32 wpb, u32 rcap, co
   if (r.status() == ST_NEED_CAPACITY) r.p(S_STATUS, (u32)ST_OK);  // resume after growth
   if (r.status() != ST_OK || r.g(S_REC_POS) >= r.rec_n()) {
     w.st((u32*)&P.st[d].status, (u32)r.status());
+    if constexpr (!HR) balance_done();
     return;
   }
   r.begin();
@@ -136,6 +142,8 @@ __device__ __forceinline__ void replay_doc(Pools P, u32 n, u32 wpb, u32 rcap, co
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // (finish()'s stores have left the wave)
   const u32 life_t1 = (u32)__builtin_amdgcn_s_memrealtime();
 #endif
+  // (whatever ended run(): the stream's end or any stop status)
+  if constexpr (!HR) balance_done();
   if constexpr (FUSE) publish_tail<L>(r.stp());  // (the document from its state pointer: d need not live through the loop)
 #ifdef CRDT_PROF
   if (r.prof_mode == 4u) {
@@ -716,6 +724,96 @@ __device__ __forceinline__ void publish_tail(const DocState* stp) {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   if (uni(O.stamp[d]) == STAMP_BIG) return;
   publish_doc<L, PUB_TAIL_DEPTH>(P, O, d, ld_karg<u32>(kp, offsetof(ReplayArgs, xw)), pub_id);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Progress balance of k_replay's waves.  The eight waves of a SIMD start together, but its issue
+// arbiter picks by priority, then by age: at equal priority the oldest wave wins every contested
+// slot, equal documents end one after the other, and the last ones replay alone at the speed of one
+// dependent chain.  So every wave sets its own priority (s_setprio, 0..3) where its
+// record window moves (Replayer::rec_window, about once per 64 records; the generated-op loop's
+// refill), from the work it has left:
+//   BAL_BOARD   longest remaining first.  The waves of a SIMD come from different workgroups, so
+//               they meet in a global board: one row per SIMD (XCC_ID and HW_ID's SE / SH / CU /
+//               SIMD fields), one slot per HW_ID.WAVE_ID, slot = launch stamp << 24 | records left.
+//               A tick stores the wave's slot, reads the row past the CU's L1, ranks itself among
+//               the slots with this launch's stamp and something left, and takes the level of its
+//               rank: the wave that fell behind is promoted at the next tick.  Slots of other
+//               launches do not match the stamp (no clearing between launches); a wave that ends
+//               writes "nothing left" (balance_done).  No wave waits for another's value: a stale
+//               or missing slot only makes a rank slightly wrong.
+//   BAL_ROTATE  the levels rotate over the wave ids in time slices of the real-time counter: no
+//               memory traffic, removes the age order of equal documents, blind to unequal ones.
+// Everything is read from the kernel-argument segment at the tick (as publish_tail does) and dies
+// in it: the replay loop carries nothing for it in registers.
+// ---------------------------------------------------------------------------------------------
+constexpr u32 BAL_ROWS = 1u << 14, BAL_SLOTS = 16u, BAL_LEFT_MAX = 0xFFFFFFu;
+enum : u32 { BAL_OFF = 0, BAL_BOARD = 1, BAL_ROTATE = 2 };
+#ifndef BAL_ROTATE_SHIFT
+#define BAL_ROTATE_SHIFT 13  // time slice of BAL_ROTATE: 2^13 ticks of the 100 MHz counter = 82 us, a few window moves
+#endif
+typedef __attribute__((address_space(1))) u32 bal_u32;  // (global_load / global_store, never flat)
+
+__device__ __forceinline__ karg_u32 balance_kargs() {
+  karg_u32 kp = (karg_u32)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("; balance: kernel-argument segment pointer" : "+s"(kp));
+  return kp;
+}
+// This wave's slot: every index field is masked to its width, so the slot lies inside the board
+// whatever the registers hold.
+__device__ __forceinline__ bal_u32* balance_row(karg_u32 kp, u32 hw) {
+  const u32 xcc = (u32)__builtin_amdgcn_s_getreg(20 | (31 << 11)) & 15u;      // XCC_ID
+  const u32 row = (xcc << 10) | (((hw >> 8) & 0xFFu) << 2) | ((hw >> 4) & 3u);  // SE, SH, CU | SIMD
+  static_assert((15u << 10 | 0xFFu << 2 | 3u) == BAL_ROWS - 1u, "row key bits");
+  return (bal_u32*)ld_karg<u32*>(kp, offsetof(ReplayArgs, bal_board)) + row * BAL_SLOTS;
+}
+// s_setprio takes an immediate and ignores EXEC: a four-way branch on a wave-uniform level
+__device__ __forceinline__ void balance_setprio(u32 level) {
+  level = uni(level);
+  asm("" : "+s"(level));  // (an SGPR value: s_cmp + s_cbranch around each s_setprio)
+  if (level == 0u) __builtin_amdgcn_s_setprio(0);
+  else if (level == 1u) __builtin_amdgcn_s_setprio(1);
+  else if (level == 2u) __builtin_amdgcn_s_setprio(2);
+  else __builtin_amdgcn_s_setprio(3);
+}
+__device__ __forceinline__ void balance_board_tick(u32 remaining) {
+  karg_u32 kp = balance_kargs();
+  const u32 mode = ld_karg<u32>(kp, offsetof(ReplayArgs, bal_mode));
+  if (mode == BAL_OFF) return;
+  const u32 hw = (u32)__builtin_amdgcn_s_getreg(4 | (31 << 11));  // HW_ID: WAVE_ID in bits 0-3
+  if (mode == BAL_ROTATE) {
+    balance_setprio(((u32)(__builtin_amdgcn_s_memrealtime() >> BAL_ROTATE_SHIFT) + hw) & 3u);
+    return;
+  }
+  bal_u32* row = balance_row(kp, hw);
+  const u32 slot = hw & (BAL_SLOTS - 1u);
+  const u32 stamp = ld_karg<u32>(kp, offsetof(ReplayArgs, bal_stamp)) << 24;
+  const u32 mine = stamp | (remaining < BAL_LEFT_MAX ? remaining : BAL_LEFT_MAX);
+  const u32 l = lane_here();
+  if (l == 0u) __hip_atomic_store(row + slot, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // lane k < 16 reads slot k (the others re-read one of them and are masked); the wave's own slot
+  // counts from its register, not from the load (another lane's store may not be visible yet)
+  const u32 v = __hip_atomic_load(row + (l & (BAL_SLOTS - 1u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const bool live = (l < BAL_SLOTS) & (l != slot) & ((v ^ stamp) - 1u < BAL_LEFT_MAX);  // this launch's, something left
+  const bool ahead = live & ((v > mine) | ((v == mine) & (l < slot)));                 // (ties: the lower slot first)
+  const u32 n = (u32)__popcll(ballot(live)) + 1u, rank = (u32)__popcll(ballot(ahead));
+  // rank 0 (most left) -> level 3; up to 4 waves one level each, up to 8 two, up to 16 four per level
+  const u32 r = rank >> (n > 8u ? 2u : n > 4u ? 1u : 0u);
+  balance_setprio(3u - (r < 3u ? r : 3u));
+}
+// A wave leaves the replay (the stream's end, any stop status, nothing to do): nothing left, and
+// priority 0 again, so the waves' publish tails run as peers.
+__device__ __forceinline__ void balance_done() {
+  karg_u32 kp = balance_kargs();
+  const u32 mode = ld_karg<u32>(kp, offsetof(ReplayArgs, bal_mode));
+  if (mode == BAL_OFF) return;
+  if (mode == BAL_BOARD) {
+    const u32 hw = (u32)__builtin_amdgcn_s_getreg(4 | (31 << 11));
+    bal_u32* row = balance_row(kp, hw);
+    const u32 stamp = ld_karg<u32>(kp, offsetof(ReplayArgs, bal_stamp)) << 24;
+    if (lane_here() == 0u) __hip_atomic_store(row + (hw & (BAL_SLOTS - 1u)), stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __builtin_amdgcn_s_setprio(0);
 }
 
 // pub_id: the host's id of the last replay launch; a document its replay wave published

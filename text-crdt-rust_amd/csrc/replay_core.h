@@ -338,6 +338,16 @@ struct Replayer {
     w.x_store_state(stp(), S_BASE);
   }
 
+  // ------------------------------------------------------------------ progress tick
+  // `remaining` records (generated ops) are left: the GPU backend sets the wave's issue priority from
+  // it (wave_gpu.h balance_tick).  Scheduling only, so a backend without the method (the CPU
+  // emulation) has nothing to do.
+  template <class X> static CRDT_HD auto tick_of(X& x, u32 remaining, int) -> decltype(x.balance_tick(remaining)) {
+    x.balance_tick(remaining);
+  }
+  template <class X> static CRDT_HD void tick_of(X&, u32, long) {}
+  CRDT_HD void balance_tick(u32 remaining) { tick_of(w, remaining, 0); }
+
   // ------------------------------------------------------------------ records
   // The op stream is read through a 64-record window [T_RB_BASE, +64) in VGPR lanes plus the
   // following 64 records, loaded ahead asynchronously: moving the window forward by d <= 64
@@ -346,6 +356,7 @@ struct Replayer {
   CRDT_HD void rec_window(u32 base) {
     u32 d = base - g(T_RB_BASE);
     u32 nn = rec_n() - base;
+    balance_tick(nn);  // (before the block ahead is requested: the tick waits for a load of its own)
     u32 ahead = nn > 64u ? nn - 64u : 0u;
     if (d <= 64u) w.rec_slide(d, recs() + base + 64u, ahead < 64u ? ahead : 64u);
     else w.rec_load2(recs() + base, nn < 64u ? nn : 64u, ahead < 64u ? ahead : 64u);
@@ -2690,6 +2701,7 @@ struct Replayer {
         u32 done = g(S_GEN_DONE), n_gen = h.w2;
         p(T_RB_BASE, 0x80000000u);
         u32 base = done;
+        balance_tick(n_gen - done);
         w.gen_draws(h.w3, base);
         // The general path goes first while there is no cached leaf yet, or while the fast-commit
         // conditions (fast_txn_ok) do not hold; once they do, every fast commit keeps them (the
@@ -2698,6 +2710,7 @@ struct Replayer {
         while (done < n_gen) {
           if (done - base >= 64u) {
             base = done;
+            balance_tick(n_gen - done);
             w.gen_draws(h.w3, base);
           }
 #ifdef CRDT_PROF

@@ -64,6 +64,9 @@ __device__ __forceinline__ u32 wave_or(u32 v) {
   return rdlane(v, 63);
 }
 
+// k_replay's progress balance (kernels.h): the wave's issue priority from the work it has left
+__device__ __forceinline__ void balance_board_tick(u32 remaining);
+
 // HR (HBM root): the root level for documents past the LDS root's capacity (ROOT_CAP_MAX
 // groups): LDS holds a top level of rows (row id, groups, visible count) and the groups live in
 // 64-slot rows in HBM (block id, slot count, visible count), with gsob[block] = row << 6 | slot.
@@ -720,6 +723,12 @@ struct WaveGPU {
   }
   __device__ __forceinline__ Rec rec_get(u32 k) const {
     return Rec{rdlane(rx, k), rdlane(ry, k), rdlane(rz, k), rdlane(rw, k)};
+  }
+  // Where the window moves (replay_core.h rec_window; the generated-op loop's refill): `remaining`
+  // records (ops) are left.  k_replay's waves set their issue priority from it (kernels.h
+  // balance_board_tick); k_replay_hr's do not.
+  __device__ __forceinline__ void balance_tick(u32 remaining) const {
+    if constexpr (!HR) balance_board_tick(remaining);
   }
   // The generator draws of ops [base, base + 64) into the window registers (lane k: hi, lo, r2 of
   // op base + k), computed lane-parallel on the vector unit; read back with rec_get.  (A GEN record
