@@ -204,6 +204,27 @@ typedef struct { uint32_t pos, del_len, ins_len, ins_off; } crdt_patch;   /* ins
  * result totals that size the result arrays.)  CRDT_E_NOMEM if an allocation fails: the engine
  * stays usable, without a diff result. */
 int crdt_diff_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* since);
+/* The patches between two versions of docs[i]: from[i] and to[i], any 0 <= from, to <= version
+ * (also inside a txn).  For a version v an item with order x is visible at v if x < v and no
+ * delete-log entry (key, target, len) covers it with a delete order key + (x - target) < v: the
+ * old-visible above, unchanged (a delete run that straddles v counts with its part below v).  The
+ * walk is the diff's, over the items of the current state in document order, with an item old if
+ * it is visible at from[i] and new if it is visible at to[i].  Old and new: closes the current
+ * patch.  Old only: adds 1 to its del_len.  New only: appended to its inserted items.  Neither:
+ * ignored, closes nothing.  A patch is a maximal run of old-only and new-only items; pos = new
+ * items before it.  Applied front to back, the patches turn the text at from[i] into the text at
+ * to[i].  from > to is allowed (the patches that take the newer text back to the older one);
+ * from == to gives no patches; to == version gives exactly the result of crdt_diff_async(from),
+ * array for array, ins_off included.
+ * The result is the diff result: this call replaces it under the rules of crdt_diff_async
+ * (stream-ordered, one wait inside, publishes first if needed, no duplicates in docs, CRDT_E_NOMEM
+ * leaves the engine usable without a diff result), and crdt_diff_counts, crdt_diff_read,
+ * crdt_last_diff_ms and crdt_rebase_async(CRDT_REBASE_FROM_DIFF) serve it without knowing which
+ * call made it.  An index whose from[i] or to[i] is above the document's version, or whose
+ * document is poisoned, has no result; the other indexes are not affected.  Does not change any
+ * document. */
+int crdt_diff_between_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* from,
+                            const uint32_t* to);
 /* Sizes of the last diff, per docs[i] of that call (syncs).  An index whose since[i] is above the
  * document's version, or whose document is poisoned, has no result: both sizes are 0xFFFFFFFF and
  * crdt_diff_read of it returns CRDT_E_ARG; the other indexes are not affected. */
@@ -509,7 +530,9 @@ int crdt_last_find_ms(crdt_engine* e, double* ms);   /* HIP events, like crdt_la
  *    per patch:
  *      new_at[p] = pos[p], new_len[p] = ins_len[p], old_len[p] = del_len[p],
  *      old_at[p] = pos[p] - (sum of ins_len[q], q < p) + (sum of del_len[q], q < p):
- *    where the patch starts in the text at since[i].
+ *    where the patch starts in the text at since[i].  (For a result of crdt_diff_between_async
+ *    the old side is the text at from[i] and the new side, "the current text" below, the text at
+ *    to[i].)
  *  - The units table is the same with unit, del_units, ins_units of the edits.  It exists only for
  *    an edits source, in that call's encoding.
  *  - Spans are ascending on both sides, and neighbouring spans are at least one kept item apart.

@@ -289,6 +289,7 @@ def lib():
     L.crdt_last_materialize_ms.argtypes = [vp, P(C.c_double)]
     L.crdt_doc_version.argtypes = [vp, u64, P(u32), P(u32)]
     L.crdt_diff_async.argtypes = [vp, u64, P(u32), P(u32)]
+    L.crdt_diff_between_async.argtypes = [vp, u64, P(u32), P(u32), P(u32)]
     L.crdt_diff_counts.argtypes = [vp, P(u32), P(u32)]
     L.crdt_diff_read.argtypes = [vp, u64, vp, P(u32), P(u32)]
     L.crdt_last_diff_ms.argtypes = [vp, P(C.c_double)]
@@ -358,7 +359,7 @@ EXPORTED_SYMBOLS = [
     "crdt_stage_local_shared", "crdt_set_content", "crdt_materialize_async", "crdt_text", "crdt_text_digest",
     "crdt_last_materialize_ms", "crdt_set_content_copies", "crdt_canon_counts", "crdt_fit", "crdt_mem_bytes", "crdt_apply_local_probed", "crdt_set_share_streams", "crdt_set_device_intern", "crdt_set_query_kernel", "crdt_device_bytes",
     "crdt_fit_note", "crdt_reseed_random_async", "crdt_digest_dev_async", "crdt_test_fail_alloc_after",
-    "crdt_doc_version", "crdt_diff_async", "crdt_diff_counts", "crdt_diff_read", "crdt_last_diff_ms",
+    "crdt_doc_version", "crdt_diff_async", "crdt_diff_between_async", "crdt_diff_counts", "crdt_diff_read", "crdt_last_diff_ms",
     "crdt_checkout_async", "crdt_checkout_lens", "crdt_checkout_read", "crdt_checkout_digest", "crdt_pos_to_loc_at",
     "crdt_loc_to_pos_at", "crdt_pos_to_loc_at_dev_async", "crdt_loc_to_pos_at_dev_async", "crdt_last_checkout_ms",
     "crdt_blame_async", "crdt_blame_counts", "crdt_blame_read", "crdt_last_blame_ms",
@@ -798,6 +799,30 @@ class Engine:
         bad = np.flatnonzero(counts[0] == 0xFFFFFFFF)
         if strict and bad.size:
             raise CrdtError(f"diff failed rc=-100 for indexes {bad.tolist()}: since above the version, or a poisoned document")
+        return [None if int(counts[0][i]) == 0xFFFFFFFF else self.diff_read(i, counts) for i in range(len(counts[0]))]
+
+    def diff_between_async(self, docs, from_, to):
+        """compute the patches from version from_[i] to version to[i] for docs[i] (no duplicates) on
+        the device; the result replaces the last diff result and is read like one (diff_counts,
+        diff_read, diff_ms, rebase_async("diff"))"""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        a = np.ascontiguousarray(from_, dtype=np.uint32)
+        b = np.ascontiguousarray(to, dtype=np.uint32)
+        if d.shape != a.shape or d.shape != b.shape or d.ndim != 1:
+            raise ValueError("diff_between: docs, from_ and to are 1-d and of equal length")
+        _check(self.L.crdt_diff_between_async(self.h, d.shape[0], _p(d), _p(a), _p(b)), "diff_between_async")
+        self._diff_n = d.shape[0]
+
+    def diff_between(self, docs, from_, to, strict: bool = True):
+        """what diff() returns, for the patches that turn the text of docs[i] at version from_[i]
+        into its text at version to[i] (either may be the later one).  An index without a result
+        (a version above the document's, a poisoned document) raises CrdtError, or is None with
+        strict=False; the other indexes are not affected."""
+        self.diff_between_async(docs, from_, to)
+        counts = self.diff_counts()
+        bad = np.flatnonzero(counts[0] == 0xFFFFFFFF)
+        if strict and bad.size:
+            raise CrdtError(f"diff_between failed rc=-100 for indexes {bad.tolist()}: a version above the document's, or a poisoned document")
         return [None if int(counts[0][i]) == 0xFFFFFFFF else self.diff_read(i, counts) for i in range(len(counts[0]))]
 
     def diff_ms(self) -> float:
@@ -1268,6 +1293,19 @@ class ListCRDT:
         """(y, hit): char positions of the text at version `v` (an earlier version()) moved to where
         they stand in the current text, or back with dir "new_to_old" (Engine.rebase)"""
         self.e.diff([0], [v])
+        self.e.rebase_async("diff")
+        p = np.ascontiguousarray(positions, dtype=np.uint32)
+        return self.e.rebase(np.zeros(p.shape[0], np.uint32), p, "chars", dir, bias)
+
+    def diff_between(self, a: int, b: int):
+        """diff_since's triple for what turns the text at version `a` into the text at version `b`
+        (any two versions up to version(), in either order)"""
+        return self.e.diff_between([0], [a], [b])[0]
+
+    def rebase_between(self, a: int, b: int, positions, dir: str = "old_to_new", bias: str = "right"):
+        """(y, hit): char positions of the text at version `a` moved to where they stand in the text
+        at version `b`, or back with dir "new_to_old" (Engine.rebase)"""
+        self.e.diff_between([0], [a], [b])
         self.e.rebase_async("diff")
         p = np.ascontiguousarray(positions, dtype=np.uint32)
         return self.e.rebase(np.zeros(p.shape[0], np.uint32), p, "chars", dir, bias)

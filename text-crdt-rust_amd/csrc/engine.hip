@@ -415,9 +415,10 @@ struct crdt_engine {
   // (host copies live until the next call: they are the source of asynchronous uploads), the
   // "deleted before since" bitmaps and the result arrays
   ResultJob<DiffRes, 2> diff;
-  std::vector<u32> diff_docs_h, diff_since_h;
+  std::vector<u32> diff_docs_h, diff_since_h, diff_to_h;
   std::vector<u64> diff_bm_h;
   DevBuf<u32> diff_docs, diff_since, diff_bm, diff_io, diff_it;
+  DevBuf<u32> diff_to, diff_bm_to;  // crdt_diff_between_async: the versions to diff to and their bitmaps
   DevBuf<u64> diff_bm_base;
   DevBuf<Patch> diff_pat;
   // checkout (crdt_checkout_async).  The arrays are copies and stay readable; the _at queries also
@@ -538,7 +539,7 @@ struct crdt_engine {
     qbuf = nullptr;
     qbuf_bytes = 0;
     each_job([](auto& j) { j.free(); });
-    free_bufs(diff_docs, diff_since, diff_bm_base, diff_bm, diff_pat, diff_io, diff_it);
+    free_bufs(diff_docs, diff_since, diff_bm_base, diff_bm, diff_pat, diff_io, diff_it, diff_to, diff_bm_to);
     free_bufs(co_docs, co_ver, co_bm_base, co_sp_base, co_bm, co_rk, co_opos, co_ord, co_text);
     free_bufs(blame_docs, blame_runs, enc_docs, enc_sp_base, enc_samples, enc_units, ln_tab, fd_pat, fd_tab);
     free_bufs(ed_docs, ed_since, ed_bm_base, ed_bm, ed_words, ed_edits, ed_units, rb_ch, rb_un);
@@ -1553,6 +1554,69 @@ struct crdt_engine {
     hipLaunchKernelGGL(k_diff<true>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, diff_view(), (u32)n);
     return diff.stop();
   }
+  // crdt_diff_between_async: run_diff with a version on either side.  k_diff_mark runs twice, on
+  // two views of the diff's buffers (from -> diff_bm, to -> diff_bm_to, the same bases); k_diff2
+  // counts and writes into the diff's own result, which is the diff result from here on.
+  int run_diff_between(u64 n, const uint32_t* dl, const uint32_t* from, const uint32_t* to) {
+    int r = set_device();
+    if (r) return r;
+    diff.drop();
+    if (!published) {
+      r = publish();
+      if (r) return r;
+    }
+    r = diff.begin(n);
+    if (r) return r;
+    if (!n) {
+      diff.valid = true;
+      return 0;
+    }
+    diff_docs_h.assign(dl, dl + n);
+    diff_since_h.assign(from, from + n);
+    diff_to_h.assign(to, to + n);
+    diff_bm_h.resize(n);
+    u64 words = 0;
+    u32 xw = 0;           // the largest listed bitmap that k_diff_mark builds in LDS
+    bool all_lds = true;  // ... and every listed one is (no bitmap word needs zeroing)
+    for (u64 i = 0; i < n; i++) {
+      diff_bm_h[i] = words;
+      u32 nw = pub_words(seg_h[dl[i]].ord_cap);
+      words += nw;
+      if (nw <= DIFF_MARK_WORDS) xw = std::max(xw, nw);
+      else all_lds = false;
+    }
+    r = grow_bufs(n, diff_docs, diff_since, diff_to, diff_bm_base);
+    if (!r) r = grow_bufs(words, diff_bm, diff_bm_to);
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(diff_docs.p, diff_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(diff_since.p, diff_since_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(diff_to.p, diff_to_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(diff_bm_base.p, diff_bm_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    r = diff.start();
+    if (r) return r;
+    if (!all_lds) {
+      HIPCHK(hipMemsetAsync(diff_bm.p, 0, words * 4, stream));
+      HIPCHK(hipMemsetAsync(diff_bm_to.p, 0, words * 4, stream));
+    }
+    Pools pv = pools_view(pools);
+    PubOut ov = pub_view();
+    DiffIO mark_to{};  // k_diff_mark reads these four only
+    mark_to.docs = diff_docs.p;
+    mark_to.since = diff_to.p;
+    mark_to.bm_base = diff_bm_base.p;
+    mark_to.bm = diff_bm_to.p;
+    hipLaunchKernelGGL(k_diff_mark, dim3((u32)n), dim3(DIFF_T), (size_t)xw * 4, stream, pv, diff_view(), (u32)n, xw);
+    hipLaunchKernelGGL(k_diff_mark, dim3((u32)n), dim3(DIFF_T), (size_t)xw * 4, stream, pv, mark_to, (u32)n, xw);
+    hipLaunchKernelGGL(k_diff2<false>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, diff2_view(), (u32)n);
+    hipLaunchKernelGGL(k_result_scan<DiffRes>, dim3(1), dim3(DIFF_SCAN_T), 0, stream, diff.res.p, (u32)n, diff.tot.p);
+    r = diff.read_totals();
+    if (!r) r = diff_pat.grow(stream, diff.tot_h[0]);
+    if (!r) r = grow_bufs(diff.tot_h[1], diff_io, diff_it);
+    if (r) return r;
+    hipLaunchKernelGGL(k_diff2<true>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, diff2_view(), (u32)n);
+    return diff.stop();
+  }
+  Diff2IO diff2_view() const { return Diff2IO{diff_view(), diff_to.p, diff_bm_to.p}; }
 
   EdIO ed_view() const {
     EdIO io{};
@@ -2901,7 +2965,7 @@ uint64_t crdt_mem_bytes(const crdt_engine* e) {
   if (!e) return 0;
   return e->pools.bytes + e->rec_cap * sizeof(Rec) + e->content_cap * 4 + e->text_cap * 4 + e->canon_alloc * 28 +
          e->pub_alloc * 4 + e->probe_cap * 16 +
-         buf_bytes(e->diff.res, e->diff_docs, e->diff_since, e->diff_bm_base, e->diff_bm, e->diff_pat, e->diff_io, e->diff_it) +
+         buf_bytes(e->diff.res, e->diff_docs, e->diff_since, e->diff_bm_base, e->diff_bm, e->diff_pat, e->diff_io, e->diff_it, e->diff_to, e->diff_bm_to) +
          buf_bytes(e->co.res, e->co_docs, e->co_ver, e->co_bm_base, e->co_sp_base, e->co_bm, e->co_rk, e->co_opos, e->co_ord, e->co_text) +
          buf_bytes(e->blame.res, e->blame_docs, e->blame_runs, e->enc.res, e->enc_docs, e->enc_sp_base, e->enc_samples, e->enc_units) +
          buf_bytes(e->ln.res, e->ln_tab, e->fd.res, e->fd_tab, e->fd_pat) +
@@ -2986,6 +3050,12 @@ int crdt_diff_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e) || (n_docs && (!docs || !since)) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
   return oom_as_nomem([&] { return e->run_diff(n_docs, docs, since); });
+}
+
+int crdt_diff_between_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* from, const uint32_t* to) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n_docs && (!docs || !from || !to)) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
+  return oom_as_nomem([&] { return e->run_diff_between(n_docs, docs, from, to); });
 }
 
 int crdt_diff_counts(crdt_engine* e, uint32_t* n_patches, uint32_t* n_ins) {

@@ -9,6 +9,7 @@
 //   k_materialize  document text from the published index + content streams (block per document)
 //   k_diff_mark / k_diff / k_result_scan  per-document text patches from a past version to now, from
 //               the published index + the delete log (block per listed document)
+//   k_diff2     (after k_diff_mark twice) the patches between two versions, from the same inputs
 //   k_co_rank / k_co_count / k_result_scan / k_co_write  the document at a past version (checkout): its
 //               items' orders and text, from the same inputs (block per listed document)
 //   k_pos_to_loc_at / k_loc_to_pos_at   the two lookups on a checked-out view (thread per query)
@@ -1410,6 +1411,355 @@ __global__ __launch_bounds__(DIFF_T) void k_diff(Pools P, PubOut O, DiffIO D, u3
   // del_len / ins_len of patch p: the D / I items from its start to the next patch's start (the
   // document's totals after the last one).  Each sweep reads its patches and their successors,
   // then writes; the next sweep's patches are untouched until then.
+  u32 np = min(c_pat, my_pat);
+  __syncthreads();
+  for (u32 p0 = 0; p0 < np; p0 += DIFF_T) {
+    u32 p = p0 + tid;
+    u32 d0 = 0, d1 = 0, i0 = 0, i1 = 0;
+    if (p < np) {
+      Patch x = pat[p];
+      d0 = x.ins_len; i0 = x.ins_off;
+      d1 = c_del; i1 = c_ins;
+      if (p + 1u < np) {
+        Patch y = pat[p + 1u];
+        d1 = y.ins_len; i1 = y.ins_off;
+      }
+    }
+    __syncthreads();
+    if (p < np) {
+      pat[p].del_len = d1 - d0;
+      pat[p].ins_len = i1 - i0;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Patches between two versions (crdt_diff_between_async): the diff's walk with both sides taken
+// from a version.  An item with order x is old when it is visible at `from` and new when it is
+// visible at `to` ("old-visible" above, once per version: x below the version and its bit clear in
+// that version's "deleted before" bitmap, k_diff_mark run twice).  K / D / I / N and the patches
+// are the diff's; pos counts the new items before the patch, which is not the published vpos.
+//
+// No closed form per span: a span's items change class at any order, so one span can hold several
+// patches.  Only order and |len| of a span matter; its classes come from the bitmaps one 32-order
+// word at a time:
+//   old = below(from) & ~bm_a,  new = below(to) & ~bm_b,  K = old & new,  C = old ^ new (D or I),
+//   X = old | new (not N).
+// A C item starts a patch when the last X item before it is a K or there is none.  Within a word
+// that is one add: (K << 1) + ~X carries every K up through the N items above it onto the next X
+// item (d2_starts); across words, spans, lanes, waves and passes the state "the last X item was a
+// C" is carried, with the counts of patches and of D, I and new items.
+// ---------------------------------------------------------------------------------------------
+struct Diff2IO {
+  DiffIO d;         // since = from, bm = the "deleted before from" bitmaps; the result as the diff's
+  const u32* to;    // [i]
+  const u32* bm_b;  // "deleted before to", at the same bm_base
+};
+#define DIFF2_LONG 256u  // spans with more orders below max(from, to) are walked by the whole wave
+
+// the orders below v among the 32 of word w
+__device__ __forceinline__ u32 below_mask(u32 w, u32 v) {
+  u32 base = w << 5;
+  return v <= base ? 0u : (v - base >= 32u ? 0xFFFFFFFFu : (1u << (v - base)) - 1u);
+}
+// one word of a span [a, b): its old, new, K, C and X items
+struct D2Word {
+  u32 o, n, K, C, X;
+};
+__device__ __forceinline__ D2Word d2_word(const u32* bma, const u32* bmb, u32 w, u32 a, u32 b, u32 from, u32 to) {
+  u32 m = range_mask(w, a, b);
+  u32 o = m & below_mask(w, from) & ~bma[w], n = m & below_mask(w, to) & ~bmb[w];
+  return D2Word{o, n, o & n, o ^ n, o | n};
+}
+// the patch starts of a word: C items whose last X predecessor in the word is a K, and the word's
+// first X item if it is a C and no patch is open before the word
+__device__ __forceinline__ u32 d2_starts(const D2Word& x, bool open) {
+  u32 s = x.C & x.X & ((x.K << 1) + ~x.X);
+  if (!open) s |= x.X & (0u - x.X) & x.C;
+  return s;
+}
+__device__ __forceinline__ bool d2_first_c(const D2Word& x) { return (x.X & (0u - x.X) & x.C) != 0u; }           // (X != 0)
+__device__ __forceinline__ bool d2_last_c(const D2Word& x) { return ((x.C >> (31u - (u32)__clz(x.X))) & 1u) != 0u; }  // (X != 0)
+// The summary of a stretch of items: any X item; its first / last X item is a C; the patch starts
+// after its first X item (counted as if a patch were open before the stretch: the first item's
+// start depends on what precedes and is added by whoever knows that); its D, I and new items.
+struct D2Sum {
+  u32 has, fc, lc, si, dd, ii, nn;
+};
+// the r-th (from 0) set bit of m (r < popc(m))
+__device__ __forceinline__ u32 nth_bit(u32 m, u32 r) {
+  u32 bit = 0;
+#pragma unroll
+  for (u32 sh = 16u; sh >= 1u; sh >>= 1) {
+    u32 c = (u32)__popc((m >> bit) & ((1u << sh) - 1u));
+    if (c <= r) {
+      r -= c;
+      bit += sh;
+    }
+  }
+  return bit;
+}
+// the patches that start in one word: pos and, for now, the D / I items before the start in
+// ins_len / ins_off (as k_diff); n0 / d0 / i0 = new, D and I items before the word
+__device__ __forceinline__ void d2_emit(u32 S, const D2Word& x, u32 p, u32 n0, u32 d0, u32 i0, Patch* pat, u32 my_pat) {
+  while (S) {
+    u32 lowm = (1u << (u32)__builtin_ctz(S)) - 1u;
+    S &= S - 1u;
+    if (p < my_pat)
+      pat[p] = Patch{n0 + (u32)__popc(x.n & lowm), 0u, d0 + (u32)__popc(x.o & ~x.n & lowm), i0 + (u32)__popc(x.n & ~x.o & lowm)};
+    p++;
+  }
+}
+
+// A long span [ua, ub) walked by the whole wave, 64 words per step in lane order.  WRITE = false:
+// its summary.  WRITE = true: `open` / p / n0 / d0 / i0 are the true state and counts before the
+// span; its patches are written by the lanes that hold their words, and its inserted items with
+// contiguous stores: lane l takes item t + l of the step's, finds its word by the 6-step search
+// over the scan (as k_diff) and its bit by a 5-step search over the word.
+template <bool WRITE>
+__device__ __forceinline__ D2Sum d2_long(const u32* bma, const u32* bmb, u32 ua, u32 ub, u32 from, u32 to, u32 l, bool open,
+                                         u32 p, u32 n0, u32 d0, u32 i0, Patch* pat, u32 my_pat, u32* io, u32* it, u32 my_ins,
+                                         bool text, const u32* src) {
+  D2Sum t{0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  u32 wl = (ub - 1u) >> 5;
+  u64 lower = (1ull << l) - 1ull;
+  for (u32 w0 = ua >> 5; w0 <= wl; w0 += 64u) {
+    u32 w = w0 + l;
+    D2Word x{0u, 0u, 0u, 0u, 0u};
+    if (w <= wl) x = d2_word(bma, bmb, w, ua, ub, from, to);
+    bool h = x.X != 0u;
+    bool lastc = h && d2_last_c(x);
+    u64 mO = ballot(lastc), mC = ballot(h && !lastc);
+    u64 lo = mO & lower, lc = mC & lower;
+    bool ob = (lo | lc) ? lo > lc : open;  // a patch is open before this lane's word
+    u32 S = d2_starts(x, ob);
+    u32 ns = (u32)__popc(S), nd = (u32)__popc(x.o & ~x.n), ni = (u32)__popc(x.n & ~x.o), nn = (u32)__popc(x.n);
+    if (!WRITE) {
+      if (!t.has && (mO | mC)) {
+        t.has = 1u;
+        t.fc = rdlane(h && d2_first_c(x) ? 1u : 0u, (u32)__builtin_ctzll(mO | mC));
+      }
+      t.si += wave_sum(ns);
+      t.dd += wave_sum(nd);
+      t.ii += wave_sum(ni);
+      t.nn += wave_sum(nn);
+    } else {
+      u32 Pi = wave_incl_scan(ns), Di = wave_incl_scan(nd), Ii = wave_incl_scan(ni), Ni = wave_incl_scan(nn);
+      d2_emit(S, x, p + Pi - ns, n0 + Ni - nn, d0 + Di - nd, i0 + Ii - ni, pat, my_pat);
+      u32 im = x.n & ~x.o;
+      u32 st = Ii - ni;  // the word's first inserted item within the step
+      u32 Tn = rdlane(Ii, 63);
+      for (u32 t0 = 0; t0 < Tn; t0 += 64u) {
+        u32 j = t0 + l;
+        u32 s = 0;
+#pragma unroll
+        for (u32 step = 32u; step >= 1u; step >>= 1) s += shfl(Ii, s + step - 1u) <= j ? step : 0u;
+        u32 sm = shfl(im, s), sst = shfl(st, s);
+        u32 o = ((w0 + s) << 5) + nth_bit(sm, j - sst);
+        u32 xi = i0 + j;
+        if (j < Tn && xi < my_ins) {
+          io[xi] = o;
+          if (text) it[xi] = src[o];
+        }
+      }
+      p += rdlane(Pi, 63);
+      n0 += rdlane(Ni, 63);
+      d0 += rdlane(Di, 63);
+      i0 += Tn;
+    }
+    if (mO | mC) open = mO > mC;
+  }
+  t.lc = (t.has && open) ? 1u : 0u;
+  return t;
+}
+
+// One block per listed document, DIFF_T canonical spans per loop pass, in document order, count
+// sweep / k_result_scan<DiffRes> / write sweep as k_diff.  Within a pass each thread summarises
+// its span word by word (D2Sum; spans past DIFF2_LONG by the whole wave), the ballots and wave
+// scans of k_diff give the state and the counts before every span, and the waves' totals meet in
+// LDS; the open state and the counts of patches, D, I and new items carry from pass to pass in
+// registers.  The write sweep then walks the words of every span in which a patch starts once
+// more, with the true state before it, and the lane writes those patches; the wave writes its
+// short spans' inserted items together and a long span's in d2_long, with contiguous stores; the
+// last sweep over the document's patches turns neighbouring starts into del_len and ins_len.
+template <bool WRITE>
+__global__ __launch_bounds__(DIFF_T) void k_diff2(Pools P, PubOut O, Diff2IO E, u32 n) {
+  u32 i = blockIdx.x;
+  if (i >= n) return;
+  const DiffIO& D = E.d;
+  u32 d = D.docs[i];
+  u32 tid = threadIdx.x, l = lane_id(), wv = uni(tid >> 6);
+  i32 stt = P.st[d].status;
+  u32 no = P.st[d].next_order, from = D.since[i], to = E.to[i];
+  u64 cb = D.cbase[d], cl = D.clen[d];
+  bool text = cb != NO_CONTENT && cl >= (u64)no;
+  if ((stt != ST_OK && stt != ST_NEED_CAPACITY) || from > no || to > no) {
+    if (!WRITE && tid == 0) D.res[i] = DiffRes{0u, 0u, DIFF_BAD, no, 0ull, 0ull};
+    return;
+  }
+  const DocSeg& sg = P.seg[d];
+  const Span* cn = O.canon + sg.canon_base;
+  u32 ns = min(O.canon_n[d], sg.canon_cap);
+  // items at or above both versions are N; every order is below ord_cap (the bitmaps' words)
+  u32 top = min(max(from, to), sg.ord_cap);
+  const u32* bma = D.bm + D.bm_base[i];
+  const u32* bmb = E.bm_b + D.bm_base[i];
+  u32 my_pat = 0, my_ins = 0;  // (WRITE) this index's counts from the first sweep: every store stays below them
+  Patch* pat = nullptr;
+  u32* io = nullptr;
+  u32* it = nullptr;
+  if (WRITE) {
+    DiffRes rs = D.res[i];
+    my_pat = rs.n_pat; my_ins = rs.n_ins;
+    pat = D.patches + rs.poff;
+    io = D.ins_order + rs.ioff;
+    it = D.ins_text + rs.ioff;
+  }
+  const u32* src = D.content + (text ? cb : 0ull);
+  __shared__ u32 s_op[DIFF_WAVES], s_d[DIFF_WAVES], s_i[DIFF_WAVES], s_n[DIFF_WAVES], s_st[DIFF_WAVES];
+  u32 c_open = 0, c_pat = 0, c_del = 0, c_ins = 0, c_new = 0;  // carried: a patch is open; patches, D, I and new items so far
+  for (u32 k0 = 0; k0 < ns; k0 += DIFF_T) {
+    u32 k = k0 + tid;
+    Span sp = k < ns ? cn[k] : Span{0, 0, 0, 0};
+    u32 a = min(sp.order, top), b = (u32)min((u64)sp.order + slen(sp), (u64)top);
+    u32 cnt = b > a ? b - a : 0u;
+    D2Sum m{0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    bool shrt = cnt != 0u && cnt <= DIFF2_LONG;
+    u32 fo = 0, hi = 0;  // (WRITE) the span's first and last inserted order
+    if (shrt) {
+      bool open = true;
+      for (u32 w = a >> 5; w <= ((b - 1u) >> 5); w++) {
+        D2Word x = d2_word(bma, bmb, w, a, b, from, to);
+        if (x.X) {
+          if (!m.has) {
+            m.has = 1u;
+            m.fc = d2_first_c(x) ? 1u : 0u;
+          }
+          m.si += (u32)__popc(d2_starts(x, open));
+          open = d2_last_c(x);
+        }
+        u32 im = x.n & ~x.o;
+        if (WRITE && im) {
+          if (!m.ii) fo = (w << 5) + (u32)__builtin_ctz(im);
+          hi = (w << 5) + 31u - (u32)__clz(im);
+        }
+        m.dd += (u32)__popc(x.o & ~x.n);
+        m.ii += (u32)__popc(im);
+        m.nn += (u32)__popc(x.n);
+      }
+      m.lc = (m.has && open) ? 1u : 0u;
+    }
+    u64 big = ballot(cnt > DIFF2_LONG);
+    for (u64 bg = big; bg;) {
+      u32 s = (u32)__builtin_ctzll(bg);
+      bg &= bg - 1ull;
+      D2Sum t = d2_long<false>(bma, bmb, rdlane(a, s), rdlane(b, s), from, to, l, true, 0u, 0u, 0u, 0u, nullptr, 0u, nullptr,
+                               nullptr, 0u, false, nullptr);
+      if (l == s) m = t;
+    }
+    // state after each span: its last X item is a C (a patch is open) or a K (none is)
+    u64 mO = ballot(m.has && m.lc), mC = ballot(m.has && !m.lc);
+    u32 Di = wave_incl_scan(m.dd), Ii = wave_incl_scan(m.ii), Ni = wave_incl_scan(m.nn);
+    if (l == 63u) {
+      s_d[wv] = Di;
+      s_i[wv] = Ii;
+      s_n[wv] = Ni;
+      s_op[wv] = (mO | mC) ? (mO > mC ? 1u : 2u) : 0u;  // (the higher lane decides) 0: no X item in this wave
+    }
+    __syncthreads();
+    u32 open_in = c_open, d_in = c_del, i_in = c_ins, n_in = c_new;
+    for (u32 w = 0; w < wv; w++) {
+      u32 op = s_op[w];
+      if (op) open_in = op == 1u;
+      d_in += s_d[w];
+      i_in += s_i[w];
+      n_in += s_n[w];
+    }
+    u64 lower = (1ull << l) - 1ull;
+    u64 lo = mO & lower, lc = mC & lower;
+    bool open_before = (lo | lc) ? lo > lc : open_in != 0u;
+    u32 nst = m.si + ((m.fc && !open_before) ? 1u : 0u);  // the patches that start in this span
+    u32 Pi = wave_incl_scan(nst);
+    if (l == 63u) s_st[wv] = Pi;
+    __syncthreads();
+    if (WRITE) {
+      u32 p = c_pat + Pi - nst;
+      for (u32 w = 0; w < wv; w++) p += s_st[w];
+      u32 Dex = d_in + Di - m.dd, Iex = i_in + Ii - m.ii, Nex = n_in + Ni - m.nn;  // D / I / new items before this span
+      if (shrt && nst != 0u) {  // the patches that start in this span: its words once more, with the true state
+        bool open = open_before;
+        u32 pp = p, n0 = Nex, d0 = Dex, i0 = Iex;
+        for (u32 w = a >> 5; w <= ((b - 1u) >> 5); w++) {
+          D2Word x = d2_word(bma, bmb, w, a, b, from, to);
+          u32 S = d2_starts(x, open);
+          d2_emit(S, x, pp, n0, d0, i0, pat, my_pat);
+          pp += (u32)__popc(S);
+          n0 += (u32)__popc(x.n);
+          d0 += (u32)__popc(x.o & ~x.n);
+          i0 += (u32)__popc(x.n & ~x.o);
+          if (x.X) open = d2_last_c(x);
+        }
+      }
+      // the short spans' inserted items: lane l takes item t + l of the wave's, so stores are
+      // contiguous; its span by the 6-step search over the scan (as k_diff).  A span whose
+      // inserted items are one run of orders (nearly all) gives the order in closed form; of
+      // another the lane walks the words to its item
+      u32 is = shrt ? m.ii : 0u;
+      u32 Is = wave_incl_scan(is);
+      u32 st = Is - is;
+      u32 Tn = rdlane(Is, 63);
+      u64 mRun = ballot(is != 0u && hi - fo + 1u == is);
+      for (u32 t0 = 0; t0 < Tn; t0 += 64u) {
+        u32 j = t0 + l;
+        u32 s = 0;
+#pragma unroll
+        for (u32 step = 32u; step >= 1u; step >>= 1) s += shfl(Is, s + step - 1u) <= j ? step : 0u;
+        u32 r = j - shfl(st, s);
+        u32 o = shfl(fo, s) + r;
+        u32 xi = shfl(Iex, s) + r;
+        bool walk = j < Tn && ((mRun >> s) & 1ull) == 0ull;
+        if (ballot(walk)) {
+          u32 sa = shfl(a, s), sb = shfl(b, s);
+          if (walk) {
+            for (u32 w = sa >> 5; w <= ((sb - 1u) >> 5); w++) {
+              D2Word x = d2_word(bma, bmb, w, sa, sb, from, to);
+              u32 im = x.n & ~x.o;
+              u32 c = (u32)__popc(im);
+              if (r < c) {
+                o = (w << 5) + nth_bit(im, r);
+                break;
+              }
+              r -= c;
+            }
+          }
+        }
+        if (j < Tn && xi < my_ins) {
+          io[xi] = o;
+          if (text) it[xi] = src[o];
+        }
+      }
+      for (u64 bg = big; bg;) {
+        u32 s = (u32)__builtin_ctzll(bg);
+        bg &= bg - 1ull;
+        d2_long<true>(bma, bmb, rdlane(a, s), rdlane(b, s), from, to, l, rdlane(open_before ? 1u : 0u, s) != 0u, rdlane(p, s),
+                      rdlane(Nex, s), rdlane(Dex, s), rdlane(Iex, s), pat, my_pat, io, it, my_ins, text, src);
+      }
+    }
+    for (u32 w = 0; w < DIFF_WAVES; w++) {
+      u32 op = s_op[w];
+      if (op) c_open = op == 1u;
+      c_del += s_d[w];
+      c_ins += s_i[w];
+      c_new += s_n[w];
+      c_pat += s_st[w];
+    }
+    __syncthreads();  // (the next pass rewrites the LDS totals)
+  }
+  if (!WRITE) {
+    if (tid == 0) D.res[i] = DiffRes{c_pat, c_ins, text ? DIFF_TEXT : 0u, no, 0ull, 0ull};
+    return;
+  }
+  // del_len / ins_len of patch p: the D / I items from its start to the next patch's start, as k_diff
   u32 np = min(c_pat, my_pat);
   __syncthreads();
   for (u32 p0 = 0; p0 < np; p0 += DIFF_T) {
