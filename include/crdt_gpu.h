@@ -664,6 +664,13 @@ int crdt_fused_publish_stats(crdt_engine* e, uint64_t* launches, uint8_t* per_do
  * Documents past the LDS root (the two-level root's kernel) are never balanced. */
 enum { CRDT_BALANCE_OFF = 0, CRDT_BALANCE_ON = 1, CRDT_BALANCE_AUTO = 2, CRDT_BALANCE_ROTATE = 3 };
 int crdt_set_replay_balance(crdt_engine* e, int mode);
+/* Window decode of the replay: a replay wave reads its stream through a 64-record window, and with
+ * the decode on it derives, once where the window moves, which compact remote records continue the
+ * typing run of the record before them (a lane mask), instead of scanning the window again at
+ * every insert.  Two builds of the same kernel, picked per launch: the same state, bit for bit.
+ * On by default (CRDT_WINDOW_DECODE=0 / 1 in the environment sets the engine's initial mode);
+ * applies to remote-only streams, from the next replay launch on. */
+int crdt_set_window_decode(crdt_engine* e, int on);
 /* Test hook: the board after the stream has drained (board: CRDT_BALANCE_BOARD_WORDS words, 16 slots
  * per SIMD row, slot = launch stamp << 24 | records left; may be NULL), the stamp of the last replay
  * launch (1..255) and the policy it ran with (0 none, 1 the board, 2 rotation).  After a launch no

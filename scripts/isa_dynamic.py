@@ -17,7 +17,7 @@ import os
 import re
 import sys
 
-SYM = os.environ.get("ISA_SYM", "_ZN4crdt8k_replayILi32ELj1EEEvNS_5PoolsEjjjPKj")  # (k_replay<32, SHAPE_REMOTE>)
+SYM = os.environ.get("ISA_SYM", "_ZN4crdt12k_replay_decILi32EEEvNS_10ReplayArgsE")  # (k_replay_dec<32>: remote-only streams)
 FILTER = int(os.environ.get("FILTER_CALL_LINE", "0"))
 FN = os.environ.get("FILTER_FN", "")
 DUMP = open(os.environ["DUMP_ADDR"], "w") if os.environ.get("DUMP_ADDR") else None  # per-instruction counts  # print this function's instructions (address, count/op)

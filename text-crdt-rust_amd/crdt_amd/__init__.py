@@ -104,9 +104,11 @@ def build_id(path: str = None) -> str:
 # the three inlined copies of that split, once per 32 double-delete entries; reloaded on the same
 # rare paths).  Same-box A/B: no cost.  A spill of a value the replay loop updates
 # would show up as more scratch stores.
-SCRATCH_STORES_MAX = {"k_replay": 4}
+SCRATCH_STORES_MAX = {"k_replay": 4, "k_replay_dec": 0}
 CODEGEN_LIMITS = {
     "k_replay": {"vgpr_count": 64, "vgpr_spill_count": 16, "private_segment_fixed_size": 32},
+    # the remote-only instance with the window decode (kernels.h k_replay_dec): the same budget, no spill
+    "k_replay_dec": {"vgpr_count": 64, "vgpr_spill_count": 0, "private_segment_fixed_size": 0},
     # the two-level-root instance (documents past the LDS root) runs at 4 waves per SIMD
     "k_replay_hr": {"vgpr_count": 128, "vgpr_spill_count": 0, "private_segment_fixed_size": 0},
     "k_publish": {"vgpr_count": 64, "vgpr_spill_count": 0, "private_segment_fixed_size": 0},
@@ -257,6 +259,8 @@ def lib():
     if hasattr(L, "crdt_set_replay_balance"):
         L.crdt_set_replay_balance.argtypes = [vp, C.c_int]
         L.crdt_debug_balance_board.argtypes = [vp, P(u32), P(u32), P(C.c_int)]
+    if hasattr(L, "crdt_set_window_decode"):
+        L.crdt_set_window_decode.argtypes = [vp, C.c_int]
     L.crdt_apply_local_probed.argtypes = [vp, u64, P(u32), P(u64), vp, vp, vp, vp, P(i32)]
     L.crdt_mem_bytes.argtypes = [vp]
     L.crdt_mem_bytes.restype = u64
@@ -371,7 +375,7 @@ EXPORTED_SYMBOLS = [
     "crdt_edits_async", "crdt_edits_counts", "crdt_edits_read", "crdt_last_edits_ms",
     "crdt_rebase_async", "crdt_rebase_counts", "crdt_rebase_read", "crdt_rebase", "crdt_rebase_dev_async", "crdt_last_rebase_ms",
     "crdt_set_fused_publish", "crdt_fused_publish_stats", "crdt_debug_vpos", "crdt_debug_publish_plan",
-    "crdt_set_replay_balance", "crdt_debug_balance_board",
+    "crdt_set_replay_balance", "crdt_debug_balance_board", "crdt_set_window_decode",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -595,6 +599,11 @@ class Engine:
         policy on launches whose waves are all resident at once; "off": never; "on" / "rotate": the
         progress board / the rotation on every launch); same state either way"""
         _check(self.L.crdt_set_replay_balance(self.h, int(self.BALANCE_MODES.get(mode, mode))), "replay_balance")
+
+    def window_decode(self, on=True):
+        """remote-only streams replay in the kernel instance that decodes typing runs once per
+        record window (default on) or in the one that scans the window at every insert; same state"""
+        _check(self.L.crdt_set_window_decode(self.h, int(on)), "window_decode")
 
     def balance_board(self):
         """(board [16384, 16] u32: per SIMD row and wave slot, launch stamp << 24 | records left;

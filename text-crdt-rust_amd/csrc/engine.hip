@@ -384,6 +384,10 @@ struct crdt_engine {
   u32* bal_board = nullptr;
   int replay_balance = getenv("CRDT_REPLAY_BALANCE") && getenv("CRDT_REPLAY_BALANCE")[0] >= '0' && getenv("CRDT_REPLAY_BALANCE")[0] <= '3'
                            ? getenv("CRDT_REPLAY_BALANCE")[0] - '0' : CRDT_BALANCE_AUTO;
+  // k_replay's window decode (wave_gpu.h decode_window): remote-only streams replay in the instance
+  // built with it, or, switched off, in the one that scans the window at every call.
+  // CRDT_WINDOW_DECODE=0|1 in the environment sets the engine's initial mode (A/B switch).
+  bool window_decode = !(getenv("CRDT_WINDOW_DECODE") && getenv("CRDT_WINDOW_DECODE")[0] == '0');
   u32 n_cus = 0;
   u32 bal_last_stamp = 0, bal_last_mode = BAL_OFF;  // of the last k_replay launch (crdt_debug_balance_board)
   u32 balance_mode(const RootClass& c, const LaunchShape& sh) const {
@@ -1154,12 +1158,14 @@ struct crdt_engine {
         ReplayArgs ra{pv, (u32)c.n, sh.wpb, sh.rcap, list, pub_view(), pubx_words, fuse ? state_id : 0u,
                       bal_board, bal_last_stamp, bal};
         if (L == 32) {
-          if (c.shape == SHAPE_REMOTE) hipLaunchKernelGGL((k_replay<32, SHAPE_REMOTE>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
+          if (c.shape == SHAPE_REMOTE && window_decode) hipLaunchKernelGGL((k_replay_dec<32>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
+          else if (c.shape == SHAPE_REMOTE) hipLaunchKernelGGL((k_replay<32, SHAPE_REMOTE>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
           else if (c.shape == SHAPE_GEN) hipLaunchKernelGGL((k_replay<32, SHAPE_GEN>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
           else if (c.shape == SHAPE_LOCAL) hipLaunchKernelGGL((k_replay<32, SHAPE_LOCAL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
           else hipLaunchKernelGGL((k_replay<32, SHAPE_ALL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
         } else {
-          if (c.shape == SHAPE_REMOTE) hipLaunchKernelGGL((k_replay<4, SHAPE_REMOTE>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
+          if (c.shape == SHAPE_REMOTE && window_decode) hipLaunchKernelGGL((k_replay_dec<4>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
+          else if (c.shape == SHAPE_REMOTE) hipLaunchKernelGGL((k_replay<4, SHAPE_REMOTE>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
           else if (c.shape == SHAPE_GEN) hipLaunchKernelGGL((k_replay<4, SHAPE_GEN>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
           else if (c.shape == SHAPE_LOCAL) hipLaunchKernelGGL((k_replay<4, SHAPE_LOCAL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
           else hipLaunchKernelGGL((k_replay<4, SHAPE_ALL>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
@@ -2165,6 +2171,8 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
   (void)hipFuncSetAttribute((const void*)k_replay<4, SHAPE_ALL>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
   (void)hipFuncSetAttribute((const void*)k_replay<32, SHAPE_REMOTE>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
   (void)hipFuncSetAttribute((const void*)k_replay<4, SHAPE_REMOTE>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+  (void)hipFuncSetAttribute((const void*)k_replay_dec<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+  (void)hipFuncSetAttribute((const void*)k_replay_dec<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
   (void)hipFuncSetAttribute((const void*)k_replay<32, SHAPE_GEN>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
   (void)hipFuncSetAttribute((const void*)k_replay<32, SHAPE_LOCAL>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
   (void)hipFuncSetAttribute((const void*)k_replay<4, SHAPE_GEN>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
@@ -2633,6 +2641,12 @@ int crdt_set_fused_publish(crdt_engine* e, int on) {
 int crdt_set_replay_balance(crdt_engine* e, int mode) {
   if (!e || mode < CRDT_BALANCE_OFF || mode > CRDT_BALANCE_ROTATE) return CRDT_E_ARG;
   e->replay_balance = mode;
+  return 0;
+}
+
+int crdt_set_window_decode(crdt_engine* e, int on) {
+  if (!e) return CRDT_E_ARG;
+  e->window_decode = on != 0;
   return 0;
 }
 

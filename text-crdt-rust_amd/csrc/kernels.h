@@ -121,14 +121,15 @@ template <int L>
 __device__ __forceinline__ void publish_tail(const DocState* stp);
 __device__ __forceinline__ void balance_done();
 
-template <int L, bool HR, u32 SH = SHAPE_ALL, bool FUSE = false>
+template <int L, bool HR, u32 SH = SHAPE_ALL, bool FUSE = false, bool DEC = false>
 __device__ __forceinline__ void replay_doc(Pools P, u32 n, u32 wpb, u32 rcap, const u32* list) {
   u32 d;
   if (!wave_doc(wpb, list, n, d)) return;
 #ifdef CRDT_PROF
   const u32 life_t0 = (u32)__builtin_amdgcn_s_memrealtime();  // (prof_mode 4: wave lifetimes)
 #endif
-  Replayer<WaveGPU<L, HR>, L> r(P, d, wave_with_root<L, HR>(rcap));
+  static_assert(!DEC || (!HR && SH == SHAPE_REMOTE), "the window decode is built into the remote-only instance");
+  Replayer<WaveGPU<L, HR>, L, DEC> r(P, d, wave_with_root<L, HR>(rcap));
   WaveGPU<L, HR>& w = r.w;
   if (r.status() == ST_NEED_CAPACITY) r.p(S_STATUS, (u32)ST_OK);  // resume after growth
   if (r.status() != ST_OK || r.g(S_REC_POS) >= r.rec_n()) {
@@ -170,6 +171,14 @@ __device__ __forceinline__ void replay_doc(Pools P, u32 n, u32 wpb, u32 rcap, co
 template <int L, u32 SH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SH == SHAPE_GEN ? CRDT_REPLAY_WAVES_GEN : CRDT_REPLAY_WAVES))) void k_replay(ReplayArgs A) {
   replay_doc<L, false, SH, true>(A.P, A.n, A.wpb, A.rcap, A.list);
+}
+// k_replay<L, SHAPE_REMOTE> reading typing runs from the decoded record window (wave_gpu.h
+// decode_window).  Remote-only streams have both kernels and the host picks one per launch
+// (crdt_set_window_decode): the switch costs the replay loop nothing, where a mode word read in the
+// kernel cost registers.  Same register budget (crdt_amd CODEGEN_LIMITS).
+template <int L>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CRDT_REPLAY_WAVES))) void k_replay_dec(ReplayArgs A) {
+  replay_doc<L, false, SHAPE_REMOTE, true, true>(A.P, A.n, A.wpb, A.rcap, A.list);
 }
 // Documents past the LDS root replay with the two-level root (wave_gpu.h HR).  They are few and
 // long, so this instance is held to 4 waves per SIMD (<= 128 VGPRs: no scratch for its extra

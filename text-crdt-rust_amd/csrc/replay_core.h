@@ -101,15 +101,24 @@ enum : u32 {
   T_AGP_KEY, T_AGP_ORDER, T_AGP_LEN,
   // ... and that non-author agent's last run (its record's copy; T_OA_LEN = 0: none)
   T_OA_KEY, T_OA_ORDER, T_OA_LEN,
-  N_SLOTS
+  // the decoded record window (W::decode_window; backends that have it): the typing continuation
+  // mask, two lanes.  Context lanes, written where the window moves: nothing of the decode is live
+  // across the replay loop.
+  W_TYP,
+  N_SLOTS = W_TYP + 2
 };
 static_assert(P_LAG + 1 < 64, "read-only slots live in the first context register");
 static_assert(S_PROF3 - S_BASE + 1 == sizeof(DocState) / 4, "DocState slot mirror");
 static_assert(F_BASE < FR_S0, "DocState and the flags live in the second context register, below the frontier heads");
 constexpr u32 FR_LANES = 128u - FR_S0;  // frontier heads kept in context lanes
 static_assert(N_SLOTS <= 192, "three context registers");
+static_assert(W_TYP >= 128, "the window mask lives in the third context register");
 
-template <class W, int L>
+// DEC: this instance reads the decoded record window (W::decode_window) where the backend has one.
+// Only an instance that replays remote-only streams is built with it (kernels.h k_replay_dec):
+// the decode covers compact remote records, and the other instances' register budgets have no
+// room for a second path.
+template <class W, int L, bool DEC = false>
 struct Replayer {
   W w;  // owned by value: its lane registers stay SSA values, never a scratch object
   // record format of the txn fast_txn is working on: compact one-record txns (RC / LC) or the
@@ -242,6 +251,7 @@ struct Replayer {
     p(F_FAST, 0);
     p(F_PRE, 0);
     p(F_GEN, 0);
+    p(W_TYP, 0); p(W_TYP + 1, 0);
   }
 
   CRDT_HD Span* leafp(u32 leaf) const { return w.template at<L>(lv(), leaf); }
@@ -348,6 +358,14 @@ struct Replayer {
   template <class X> static CRDT_HD void tick_of(X&, u32, long) {}
   CRDT_HD void balance_tick(u32 remaining) { tick_of(w, remaining, 0); }
 
+  // ------------------------------------------------------------------ window decode
+  // The window's typing-run predicate, decoded once where the window moves (W::decode_window: a
+  // mask in the W_TYP context lanes) and read by typing_run instead of a scan per call.  Optional
+  // like the tick: a backend without the methods (the CPU emulation) keeps the scan.
+  template <class X> static constexpr auto has_decode_of(int) -> decltype(&X::decode_window, &X::win_mask, true) { return true; }
+  template <class X> static constexpr bool has_decode_of(long) { return false; }
+  static constexpr bool has_decode = DEC && has_decode_of<W>(0);
+
   // ------------------------------------------------------------------ records
   // The op stream is read through a 64-record window [T_RB_BASE, +64) in VGPR lanes plus the
   // following 64 records, loaded ahead asynchronously: moving the window forward by d <= 64
@@ -361,6 +379,7 @@ struct Replayer {
     if (d <= 64u) w.rec_slide(d, recs() + base + 64u, ahead < 64u ? ahead : 64u);
     else w.rec_load2(recs() + base, nn < 64u ? nn : 64u, ahead < 64u ? ahead : 64u);
     p(T_RB_BASE, base);
+    if constexpr (has_decode) w.decode_window(nn < 64u ? nn : 64u, W_TYP);
   }
   // The record at pos, moving the window so that it holds [pos, pos + 3) (a whole general-form
   // one-op txn).  The ONLY place the window moves: its registers then have one definition in the
@@ -1701,7 +1720,21 @@ struct Replayer {
     u32 nt = 1u;
     total = remote ? (o.w0 & 0x0FFFFFFFu) : o.w3;
     if (!nv) return nt;
-    nt = w.typing_scan(b0, nv, remote, cpt, agent, ow1, o.w3, total);
+    // A compact remote txn reads the run from the decoded window's mask (W::decode_window) instead
+    // of scanning.  The mask tests each record against the one before it, where typing_scan tests
+    // it against this call's agent, ow1 and o.w3; the two agree because
+    //  (1) for a compact remote record both callers pass ow1 = agent | ra << 16 with ra derived
+    //      from o.w3 as the scan derives it, so the scan's uniform op-word term is always 0;
+    //  (2) o.w3 is the window record's own w3 at b0 (fast_txn builds `o` from that record), so
+    //      "the same origin_right as the record before" chains back to it, as the author does;
+    //  (3) the window registers change only in rec_window, which decodes them at once (this
+    //      instance replays no generated ops, whose draws reuse the registers).
+    bool decoded = false;
+    if constexpr (has_decode) {
+      decoded = (cpt & remote) != 0u;
+      if (decoded) nt = w.typing_scan_m(b0, W_TYP, total);
+    }
+    if (!decoded) nt = w.typing_scan(b0, nv, remote, cpt, agent, ow1, o.w3, total);
     u32 per = per_txn(remote), rn = rec_n();
     u32 pos0 = g(T_RB_BASE) + b0;
     u32 end = g(T_RB_BASE) + nv;  // records scanned so far: [pos0, end)

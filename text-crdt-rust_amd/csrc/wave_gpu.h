@@ -863,6 +863,56 @@ struct WaveGPU {
     uint4 v = rec_lane_load(p, nv);
     return delete_scan_r(v.x, v.y, v.z, v.w, 0u, nv, remote, compact, agent, delta);
   }
+  // ---------------------------------------------------------------- window decode
+  // Whether a compact remote record continues the typing run of the record before it depends only
+  // on the two records, and about 3.5 fast-path calls share a window: decode_window() tests it
+  // once where the window moves (replay_core.h rec_window), lane-parallel.  Lane k tests record k
+  // against record k-1 (one DPP wave shift per word, no LDS shuffle) with typing_scan_r's compact
+  // remote terms -- an RC insert of the previous record's author, seq contiguous with it,
+  // origin_left its own previous item, the same origin_right, len != 0; the author, origin_right
+  // and the op word chain back to the run's first record, which the caller checked -- and the
+  // predicate is ballotted into a lane mask kept in two context lanes (s_typ).  Bit 0 and the
+  // bits from nv (valid records) up are clear, so a run's length from slot b0 is a shift and a
+  // find-first-bit; a run that crosses into the window arrives by typing_scan_at, which reads no
+  // mask.  The run's total length needs no prefix sum: seqs are contiguous, so it is the last
+  // record's seq + len less the first record's seq.  A set bit k needs record k to be an RC record
+  // that matches record k-1, so from a checked RC record the chain is valid whatever else the
+  // window holds (general-form txns, another author).
+  // lane k: lane k-1's v (lane 0: 0).  The result is made opaque so that it stays a v_mov_b32_dpp.
+  // Observed with ROCm's clang (profiles/dpp_wave_shr_sub.txt: source, disassembly and output of a
+  // few-line kernel): left to the DPP combiner, own - shifted became one v_subrev_u32_dpp with the
+  // same register as both operands, and that kernel printed -1 where +1 was expected on an
+  // MI355X.  Whether the combine or the instruction is at fault was not looked into.
+  __device__ __forceinline__ static u32 wave_shr1(u32 v) {
+    u32 r = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false);  // wave_shr:1
+    asm("" : "+v"(r));
+    return r;
+  }
+  __device__ __forceinline__ void decode_window(u32 nv, u32 s_typ) {
+    u32 l = lane();
+    u32 p0 = wave_shr1(rx), p1 = wave_shr1(ry), p3 = wave_shr1(rw);
+    // the equality terms folded into one word (typing_scan_r)
+    u32 dt = ((rx & RC_HDR_MASK) ^ ((REC_RC << 28) | (p0 & 0xFFFFu))) | (ry ^ (p1 + ((p0 >> 16) & 0x7FFu))) |
+             (rz ^ (ry - 1u)) | (rw ^ p3);
+    bool in = l - 1u < nv - 1u;  // 1 <= l < nv
+    u64 mt = ballot(in & (dt == 0u) & ((rx & (0x7FFu << 16)) != 0u));
+    xs(s_typ, (u32)mt); xs(s_typ + 1u, (u32)(mt >> 32));
+  }
+  // (the mask slots live in x2: read directly)
+  __device__ __forceinline__ u64 win_mask(u32 s) const { return ((u64)rdlane(x2, s - 127u) << 32) | rdlane(x2, s - 128u); }
+  // records of the run that starts at slot b0 (<= 62) of a mask: 1 + the set bits that follow it
+  __device__ __forceinline__ static u32 mask_run(u64 m, u32 b0) {
+    u64 stop = ~m & (~1ull << b0);
+    return (stop ? (u32)__builtin_ctzll(stop) : 64u) - b0;
+  }
+  // typing_scan for compact remote records from the decoded window
+  __device__ __forceinline__ u32 typing_scan_m(u32 b0, u32 s_typ, u32& total) const {
+    u32 n = mask_run(win_mask(s_typ), b0);
+    u32 e = b0 + n - 1u;
+    total = rdlane(ry, e) + ((rdlane(rx, e) >> 16) & 0x7FFu) - rdlane(ry, b0);
+    return n;
+  }
+
   // advance_branch_by for a remote txn (doc.rs:34-48), one frontier head and one parent per lane
   // (nfr, np <= 64): head 0 is f0 (the write-back tail), heads 1.. live at f[1..].  Returns 0 if a
   // head is `first` (the txn is known), INVALID if the new frontier would pass cap, else the new
