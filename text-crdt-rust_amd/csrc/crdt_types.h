@@ -191,8 +191,13 @@ struct Rec { u32 w0, w1, w2, w3; };
 // RC      w0 = kind<<28 | del<<27 | len<<16 (11 b, 1..2047) | author
 //                                       w1 = seq   w2 = ins: origin_left seq, del: target seq
 //                                                  w3 = ins: origin_right seq
+//                                                       del: delete-run hint, back<<31 | m
 //         one RemoteOp; its origins / target are the author's items (a seq of 0xFFFFFFFF names
-//         ROOT); the one parent is (author, seq - 1)
+//         ROOT); the one parent is (author, seq - 1).  The hint (host_plan.h hint_delete_runs):
+//         the m records from this one on are one-item deletes by this author, seqs rising by 1,
+//         targets moving by +1 (back = 0) or -1 (back = 1); m = 1 for a run of one and for
+//         len != 1, 0 reads as 1.  A lower bound that the replay trusts (fast_deletes), not part
+//         of the txn: expand_rc ignores it
 // LC      w0 = kind<<28 | agent (16 b)  w1 = pos   w2 = del   w3 = ins   (one LocalOp)
 // PROBE   w0 = kind<<28                 w1 = pos   w2 = agent w3 = seq
 //         answers pos -> (agent, seq) and (agent, seq) -> (pos, deleted) on the state reached so far

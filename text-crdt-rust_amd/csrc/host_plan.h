@@ -174,9 +174,41 @@ inline void encode_local_txn(std::vector<Rec>& out, StreamNeeds& nd, u32 agent, 
   nd.agent_txn(agent);
 }
 
+// Delete-run hints (crdt_types.h RC): every compact remote delete record from `from` on gets, in
+// its free w3, the length m of the maximal run of one-item deletes that starts at it -- the
+// records j .. j+m-1 are RC deletes of one item by one author, their seqs rise by 1 and their
+// target seqs move by one constant step d, +1 (forward delete) or -1 (backspace): the terms of
+// the replay's delete scan, pairwise -- as w3 = (d == -1) << 31 | m.  A record of another length
+// and a run's last record get m = 1.  The run is a property of the records alone, so it is
+// measured here, once, and fast_deletes reads it instead of scanning on every call.  A hint may
+// fall short (a run that goes on in a batch staged later is cut at this batch's end and picked
+// up by the next call) but never counts a record that does not continue the run.  One backward
+// pass: the run at j is the run at j+1 plus one when the step into j+1 is that run's step.
+inline void hint_delete_runs(std::vector<Rec>& out, size_t from) {
+  const u32 DEL1 = (REC_RC << 28) | (1u << 27) | (1u << 16);  // kind | del | len 1 (w0 without the author)
+  u32 mn = 0, dn = 0;  // the run that starts at j+1 (0: not an RC delete) and its step (0: a run of one)
+  for (size_t j = out.size(); j-- > from;) {
+    Rec& r = out[j];
+    if ((r.w0 >> 27) != ((REC_RC << 1) | 1u)) { mn = 0; continue; }
+    u32 m = 1, d = 0;
+    if (mn && (r.w0 & ~0xFFFFu) == DEL1 && out[j + 1].w0 == r.w0 && out[j + 1].w1 == r.w1 + 1u) {
+      u32 step = out[j + 1].w2 - r.w2;
+      if (step == 1u || step == 0xFFFFFFFFu) {
+        d = step;
+        m = (mn >= 2u && dn == step) ? mn + 1u : 2u;
+        if (m > 0x7FFFFFFFu) m = 0x7FFFFFFFu;
+      }
+    }
+    r.w3 = ((d == 0xFFFFFFFFu ? 1u : 0u) << 31) | m;
+    mn = m;
+    dn = d;
+  }
+}
+
 // Encode a remote wire batch for one document, interning authors in txn order exactly as
 // apply_remote_txn does (doc.rs:243 get_or_create for the author; doc.rs:237 lookup for ids).
 inline void encode_remote(std::vector<Rec>& out, StreamNeeds& nd, AgentTable& at, const WireView& wv) {
+  const size_t from = out.size();
   std::vector<u32> cache(wv.names.size(), 0xFFFFFFFFu);
   for (const WireTxnView& t : wv.txns) {
     size_t before = at.names.size();
@@ -249,6 +281,7 @@ inline void encode_remote(std::vector<Rec>& out, StreamNeeds& nd, AgentTable& at
     nd.remote_parents += t.n_parents;
     nd.agent_txn(author);
   }
+  hint_delete_runs(out, from);
 }
 
 // A PROBE record: after the txns before it, answer pos_to_loc(pos) and loc_to_pos(agent, seq).

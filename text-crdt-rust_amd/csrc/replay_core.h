@@ -1890,9 +1890,10 @@ struct Replayer {
   // Delete txns: the one at b0 (l items at `off` of entry idx) and, when it deletes one item, the
   // run of one-item delete txns that follows it in the prefetch block -- backspacing (each
   // deletes the item before the previous one) or forward deleting (the item after) -- validated
-  // lane-parallel (W::delete_scan).  Each delete is applied to the leaf exactly as apply_txn
-  // would (leaf_delete); the RLE tables, the order map and the txn log are updated once for the
-  // run.  Returns records consumed (0: nothing applied).
+  // lane-parallel (W::delete_scan), or, for compact remote records, taken from the hint the
+  // encoder left in the record (host_plan.h hint_delete_runs).  Each delete is applied to the
+  // leaf exactly as apply_txn would (leaf_delete); the RLE tables, the order map and the txn log
+  // are updated once for the run.  Returns records consumed (0: nothing applied).
   CRDT_HD u32 fast_deletes(u32 b0, u32 nv, u32 remote, u32 agent, u32 idx, u32 off, u32 l, u32 first, const Rec& o) {
 #ifdef CRDT_PROF
     u64 pt0 = w.clock();  // detail (prof_mode 3): cycles of run detection / first segment / leaf-split loop / tail
@@ -1912,55 +1913,67 @@ struct Replayer {
     }
     u32 k = 1, back = 0;
     u32 key = g(T_AGL_KEY);
-    // a run of one-item deletes follows?  The shape checks fold into one integer (one branch, so
-    // the two results have one merge), the next txn's target / pos read unconditionally (a window
-    // lane; ignored unless the checks pass)
-    u32 delta;
-    u32 has_next = b0 + 2u * per <= nv ? 1u : 0u;
-    u32 bn = has_next ? b0 + per : b0;  // (a valid window slot either way)
-    if (cpt) {  // compact records: the next txn's target seq (RC w2) / pos (LC w1) read directly
-      Rec r2 = w.rec_get(bn);
-      delta = remote ? r2.w2 - o.w2 : r2.w1 - o.w1;
+    if (remote && cpt) {
+      // compact remote: the run that starts at this record was measured when the stream was
+      // encoded (host_plan.h hint_delete_runs: w3 = backspace << 31 | records, a lower bound that
+      // never crosses the staged batch's end), so no record is read and nothing is scanned here.
+      // What depends on the document's state is checked as for a scanned run: the targets stay
+      // in this entry and in the author's last item_orders run (the record's author is `agent`
+      // by construction).  w3 == 0 (no hint) reads as a run of one.
+      u32 m = o.w3 & 0x7FFFFFFFu;
+      u32 bad = (l ^ 1u) | (m < 2u ? 1u : 0u) | (o.w2 - key >= g(T_AGL_LEN) ? 1u : 0u);
+      if (opq(bad) == 0u) {
+        back = o.w3 >> 31;
+        u32 room = back ? off + 1u : (u32)w.cget_len(idx) - off;
+        u32 r2 = back ? o.w2 - key + 1u : key + g(T_AGL_LEN) - o.w2;
+        room = room < r2 ? room : r2;
+        k = m < room ? m : room;
+      }
     } else {
-      Rec o2 = op_at(bn, remote);
-      delta = remote ? o2.w2 - o.w2 : o2.w1 - o.w1;
-    }
-    u32 bk = delta == 0xFFFFFFFFu ? 1u : 0u;
-    u32 bad = (l ^ 1u) | (has_next ^ 1u) | ((delta != (remote ? 1u : 0u) ? 1u : 0u) & (bk ^ 1u));
-    if (remote) bad |= ((o.w1 & 0xFFFFu) ^ agent) | (o.w2 - key >= g(T_AGL_LEN) ? 1u : 0u);
-    if (opq(bad) == 0u) {
-      back = opq(bk);
-      {
-        u32 room = back ? off + 1u : (u32)w.cget_len(idx) - off;  // targets stay in this entry
-        if (remote) {  // ... and in the author's last item_orders run (contiguous orders)
-          u32 r2 = back ? o.w2 - key + 1u : key + g(T_AGL_LEN) - o.w2;
-          room = room < r2 ? room : r2;
+      // a run of one-item deletes follows?  The shape checks fold into one integer (one branch, so
+      // the two results have one merge), the next txn's target / pos read unconditionally (a window
+      // lane; ignored unless the checks pass)
+      u32 delta;
+      u32 has_next = b0 + 2u * per <= nv ? 1u : 0u;
+      u32 bn = has_next ? b0 + per : b0;  // (a valid window slot either way)
+      if (cpt) {  // compact local records: the next txn's pos (LC w1) read directly
+        Rec r2 = w.rec_get(bn);
+        delta = r2.w1 - o.w1;
+      } else {
+        Rec o2 = op_at(bn, remote);
+        delta = remote ? o2.w2 - o.w2 : o2.w1 - o.w1;
+      }
+      u32 bk = delta == 0xFFFFFFFFu ? 1u : 0u;
+      u32 bad = (l ^ 1u) | (has_next ^ 1u) | ((delta != (remote ? 1u : 0u) ? 1u : 0u) & (bk ^ 1u));
+      if (remote) bad |= ((o.w1 & 0xFFFFu) ^ agent) | (o.w2 - key >= g(T_AGL_LEN) ? 1u : 0u);
+      if (opq(bad) == 0u) {
+        back = opq(bk);
+        {
+          u32 room = back ? off + 1u : (u32)w.cget_len(idx) - off;  // targets stay in this entry
+          if (remote) {  // ... and in the author's last item_orders run (contiguous orders)
+            u32 r2 = back ? o.w2 - key + 1u : key + g(T_AGL_LEN) - o.w2;
+            room = room < r2 ? room : r2;
+          }
+          k = w.delete_scan(b0, nv, remote, cpt, agent, delta);
+          // the run may go on past the window: slide the window to its last txn and scan on
+          u32 rn = rec_n();
+          u32 pos0 = g(T_RB_BASE) + b0;
+          u32 end = g(T_RB_BASE) + nv;
+          while (true) {
+            if (k >= room) break;
+            if (pos0 + (k + 1u) * per <= end) break;
+            if (end >= rn) break;
+            u32 last = pos0 + (k - 1u) * per;
+            u32 n = rn - last < 64u ? rn - last : 64u;
+            u32 n2 = w.delete_scan_at(w.at(recs(), last), n, remote, cpt, agent, delta);
+            end = last + n;
+            if (n2 <= 1u) break;
+            k += n2 - 1u;
+          }
+          k = k < room ? k : room;
         }
-        k = w.delete_scan(b0, nv, remote, cpt, agent, delta);
-        // the run may go on past the window: slide the window to its last txn and scan on
-        u32 rn = rec_n();
-        u32 pos0 = g(T_RB_BASE) + b0;
-        u32 end = g(T_RB_BASE) + nv;
-        while (true) {
-          if (k >= room) break;
-          if (pos0 + (k + 1u) * per <= end) break;
-          if (end >= rn) break;
-          u32 last = pos0 + (k - 1u) * per;
-          u32 n = rn - last < 64u ? rn - last : 64u;
-          u32 n2 = w.delete_scan_at(w.at(recs(), last), n, remote, cpt, agent, delta);
-          end = last + n;
-          if (n2 <= 1u) break;
-          k += n2 - 1u;
-        }
-#ifdef CRDT_PROF
-
-#endif
-        k = k < room ? k : room;
       }
     }
-#ifdef CRDT_PROF
-
-#endif
     if (g(K_MAP) - first < k * l) return 0;
     // delete-log room: a backspace run logs one run per item, a forward run coalesces into one
     // (was k for both: after crdt_fit the log's room is the stream's own count, so every forward
@@ -2448,7 +2461,9 @@ struct Replayer {
       ins = del ^ 1u;
       u32 ra = r.w3 == 0xFFFFFFFFu ? ROOT_AGENT : agent;
       // the op record as expand_rc's insert form; the delete paths read only its author (low half
-      // of w1) and target seq (w2), which the two forms share, so no per-field select
+      // of w1) and target seq (w2), which the two forms share, so no per-field select.  (A delete
+      // record's w3 is its delete-run hint, not an origin: `ra` and o.w1's high half mean nothing
+      // then and no delete path reads them; fast_deletes reads o.w3 as the hint.)
       o = Rec{(REC_RINS << 28) | l, agent | (ra << 16), r.w2, r.w3};
       if (l == 0u) return 0;
       if (!fast_txn_ok(agent, seq, first)) return 0;

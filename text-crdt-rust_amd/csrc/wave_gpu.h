@@ -803,11 +803,11 @@ struct WaveGPU {
   // txns (>= 1; the txn at b0 was checked by the caller).
   __device__ __forceinline__ u32 delete_scan_r(u32 X, u32 Y, u32 Z, u32 Q, u32 b0, u32 nv, u32 remote, u32 compact, u32 agent, u32 delta) const {
     u32 l = lane();
-    if (compact) {  // one record per txn: lane k against record k-1
-      u32 p1 = shfl(Y, l - 1u), p2 = shfl(Z, l - 1u);
+    if (compact) {  // LC, one record per txn: lane k against record k-1.  (Compact remote runs are
+                    // never scanned: fast_deletes reads their length from the record's w3 hint.)
+      u32 p1 = shfl(Y, l - 1u);
       // the equality terms folded into one word (one compare instead of a mask AND per term)
-      u32 d = remote ? ((X ^ ((REC_RC << 28) | (1u << 27) | (1u << 16) | agent)) | (Y ^ (p1 + 1u)) | (Z ^ (p2 + delta)))
-                     : ((X ^ ((REC_LC << 28) | agent)) | (Z ^ 1u) | Q | (Y ^ (p1 + delta)));
+      u32 d = (X ^ ((REC_LC << 28) | agent)) | (Z ^ 1u) | Q | (Y ^ (p1 + delta));
       bool ok = d == 0u;
       u64 stop = ballot(!ok || l >= nv) & (~1ull << b0);
       u32 f = stop ? (u32)__builtin_ctzll(stop) : 64u;
