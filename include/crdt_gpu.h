@@ -664,6 +664,19 @@ int crdt_fused_publish_stats(crdt_engine* e, uint64_t* launches, uint8_t* per_do
  * Documents past the LDS root (the two-level root's kernel) are never balanced. */
 enum { CRDT_BALANCE_OFF = 0, CRDT_BALANCE_ON = 1, CRDT_BALANCE_AUTO = 2, CRDT_BALANCE_ROTATE = 3 };
 int crdt_set_replay_balance(crdt_engine* e, int mode);
+/* The rotation's level map: which wave slots of a SIMD hold which of the four levels in a time
+ * slice (eight slots share four levels, and the arbiter breaks a tie by age, so what a map chooses
+ * is who ties with whom).  0: level = (slice + slot) & 3, slots w and w + 4 tied for the whole
+ * launch; 1: pairs of neighbouring slots, a slot tied with its upper and its lower neighbour in
+ * turn; 2: groups of one, two and three slots, chosen so that the slots' mean places in the
+ * arbiter's order lie closest together (the default: equal documents end closest together and
+ * the launch is shortest).  Every map gives every slot each level a quarter of the time.
+ * Scheduling only: the same state, bit for bit.  CRDT_BALANCE_MAP=0..2 in the environment sets the
+ * engine's initial map; applies from the next replay launch on.  The policy that
+ * crdt_debug_balance_board reports is 2 (rotation) whatever the map. */
+#define CRDT_BALANCE_MAPS 3
+#define CRDT_BALANCE_MAP_DEFAULT 2
+int crdt_set_balance_map(crdt_engine* e, int map);
 /* Window decode of the replay: a replay wave reads its stream through a 64-record window, and with
  * the decode on it derives, once where the window moves, which compact remote records continue the
  * typing run of the record before them (a lane mask), instead of scanning the window again at

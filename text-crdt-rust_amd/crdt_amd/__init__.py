@@ -29,6 +29,9 @@ ROOT_AGENT = 0xFFFF
 ROOT_ORDER = 0xFFFFFFFF
 
 
+BALANCE_MAPS = 3  # level maps of the replay's rotation policy (csrc/balance_levels.h BALANCE_MAPS)
+
+
 class CrdtError(RuntimeError):
     pass
 
@@ -261,6 +264,8 @@ def lib():
         L.crdt_debug_balance_board.argtypes = [vp, P(u32), P(u32), P(C.c_int)]
     if hasattr(L, "crdt_set_window_decode"):
         L.crdt_set_window_decode.argtypes = [vp, C.c_int]
+    if hasattr(L, "crdt_set_balance_map"):
+        L.crdt_set_balance_map.argtypes = [vp, C.c_int]
     L.crdt_apply_local_probed.argtypes = [vp, u64, P(u32), P(u64), vp, vp, vp, vp, P(i32)]
     L.crdt_mem_bytes.argtypes = [vp]
     L.crdt_mem_bytes.restype = u64
@@ -375,7 +380,7 @@ EXPORTED_SYMBOLS = [
     "crdt_edits_async", "crdt_edits_counts", "crdt_edits_read", "crdt_last_edits_ms",
     "crdt_rebase_async", "crdt_rebase_counts", "crdt_rebase_read", "crdt_rebase", "crdt_rebase_dev_async", "crdt_last_rebase_ms",
     "crdt_set_fused_publish", "crdt_fused_publish_stats", "crdt_debug_vpos", "crdt_debug_publish_plan",
-    "crdt_set_replay_balance", "crdt_debug_balance_board", "crdt_set_window_decode",
+    "crdt_set_replay_balance", "crdt_debug_balance_board", "crdt_set_window_decode", "crdt_set_balance_map",
     # include/crdt_trace.h (host-only trace ingestion)
     "crdt_trace_load", "crdt_trace_parse", "crdt_trace_sizes", "crdt_trace_copy", "crdt_trace_free",
 ]
@@ -599,6 +604,11 @@ class Engine:
         policy on launches whose waves are all resident at once; "off": never; "on" / "rotate": the
         progress board / the rotation on every launch); same state either way"""
         _check(self.L.crdt_set_replay_balance(self.h, int(self.BALANCE_MODES.get(mode, mode))), "replay_balance")
+
+    def set_balance_map(self, bmap: int):
+        """the rotation policy's level map (0 .. BALANCE_MAPS - 1, csrc/balance_levels.h: which waves
+        of a SIMD tie at a priority level in a time slice); same state whatever the map"""
+        _check(self.L.crdt_set_balance_map(self.h, int(bmap)), "set_balance_map")
 
     def window_decode(self, on=True):
         """remote-only streams replay in the kernel instance that decodes typing runs once per

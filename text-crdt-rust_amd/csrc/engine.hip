@@ -384,6 +384,10 @@ struct crdt_engine {
   u32* bal_board = nullptr;
   int replay_balance = getenv("CRDT_REPLAY_BALANCE") && getenv("CRDT_REPLAY_BALANCE")[0] >= '0' && getenv("CRDT_REPLAY_BALANCE")[0] <= '3'
                            ? getenv("CRDT_REPLAY_BALANCE")[0] - '0' : CRDT_BALANCE_AUTO;
+  // the rotation's level map (balance_levels.h; crdt_set_balance_map).  CRDT_BALANCE_MAP=0..2 in the
+  // environment sets the engine's initial map (A/B switch).
+  u32 balance_map = getenv("CRDT_BALANCE_MAP") && getenv("CRDT_BALANCE_MAP")[0] >= '0' && getenv("CRDT_BALANCE_MAP")[0] < (char)('0' + BALANCE_MAPS)
+                        ? (u32)(getenv("CRDT_BALANCE_MAP")[0] - '0') : CRDT_BALANCE_MAP_DEFAULT;
   // k_replay's window decode (wave_gpu.h decode_window): remote-only streams replay in the instance
   // built with it, or, switched off, in the one that scans the window at every call.
   // CRDT_WINDOW_DECODE=0|1 in the environment sets the engine's initial mode (A/B switch).
@@ -1156,7 +1160,7 @@ struct crdt_engine {
         const u32 bal = balance_mode(c, sh);
         bal_last_mode = std::max(bal_last_mode, bal);
         ReplayArgs ra{pv, (u32)c.n, sh.wpb, sh.rcap, list, pub_view(), pubx_words, fuse ? state_id : 0u,
-                      bal_board, bal_last_stamp, bal};
+                      bal_board, bal_last_stamp, bal, balance_table(balance_map)};
         if (L == 32) {
           if (c.shape == SHAPE_REMOTE && window_decode) hipLaunchKernelGGL((k_replay_dec<32>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
           else if (c.shape == SHAPE_REMOTE) hipLaunchKernelGGL((k_replay<32, SHAPE_REMOTE>), dim3(blocks), dim3(64 * sh.wpb), sh.lds, stream, ra);
@@ -2641,6 +2645,13 @@ int crdt_set_fused_publish(crdt_engine* e, int on) {
 int crdt_set_replay_balance(crdt_engine* e, int mode) {
   if (!e || mode < CRDT_BALANCE_OFF || mode > CRDT_BALANCE_ROTATE) return CRDT_E_ARG;
   e->replay_balance = mode;
+  return 0;
+}
+
+static_assert(BALANCE_MAPS == CRDT_BALANCE_MAPS && BALANCE_MAPS <= 10 && CRDT_BALANCE_MAP_DEFAULT < CRDT_BALANCE_MAPS, "crdt_gpu.h and balance_levels.h");
+int crdt_set_balance_map(crdt_engine* e, int map) {
+  if (!e || map < 0 || map >= (int)BALANCE_MAPS) return CRDT_E_ARG;
+  e->balance_map = (u32)map;
   return 0;
 }
 

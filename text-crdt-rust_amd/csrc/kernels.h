@@ -18,6 +18,7 @@
 #pragma once
 #include "replay_core.h"
 #include "wave_gpu.h"
+#include "balance_levels.h"
 
 namespace crdt {
 
@@ -116,6 +117,7 @@ struct ReplayArgs {
   u32* bal_board;  // [BAL_ROWS][BAL_SLOTS]
   u32 bal_stamp;   // this launch's stamp, 1..255
   u32 bal_mode;    // BAL_*
+  u64 bal_table;   // BAL_ROTATE's level map (balance_levels.h balance_table)
 };
 template <int L>
 __device__ __forceinline__ void publish_tail(const DocState* stp);
@@ -754,6 +756,8 @@ __device__ __forceinline__ void publish_tail(const DocState* stp) {
 //               or missing slot only makes a rank slightly wrong.
 //   BAL_ROTATE  the levels rotate over the wave ids in time slices of the real-time counter: no
 //               memory traffic, removes the age order of equal documents, blind to unequal ones.
+//               Which wave ids tie at a level in a slice is the level map's choice
+//               (balance_levels.h, ReplayArgs::bal_table).
 // Everything is read from the kernel-argument segment at the tick (as publish_tail does) and dies
 // in it: the replay loop carries nothing for it in registers.
 // ---------------------------------------------------------------------------------------------
@@ -792,7 +796,9 @@ __device__ __forceinline__ void balance_board_tick(u32 remaining) {
   if (mode == BAL_OFF) return;
   const u32 hw = (u32)__builtin_amdgcn_s_getreg(4 | (31 << 11));  // HW_ID: WAVE_ID in bits 0-3
   if (mode == BAL_ROTATE) {
-    balance_setprio(((u32)(__builtin_amdgcn_s_memrealtime() >> BAL_ROTATE_SHIFT) + hw) & 3u);
+    // (the level map's table: kernel-argument words, read here and dead after the level; SGPR arithmetic)
+    const u64 table = ld_karg<u64>(kp, offsetof(ReplayArgs, bal_table));
+    balance_setprio(balance_level_in(table, (u32)(__builtin_amdgcn_s_memrealtime() >> BAL_ROTATE_SHIFT), hw));
     return;
   }
   bal_u32* row = balance_row(kp, hw);
