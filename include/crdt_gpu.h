@@ -271,6 +271,29 @@ typedef struct { uint32_t pos, del_len, ins_len, unit, del_units, ins_units, ins
  * an allocation fails: the engine stays usable, without an edits result, and the same call then
  * succeeds. */
 int crdt_edits_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* since, int enc);
+/* The edits between two versions of docs[i]: from[i] and to[i], any 0 <= from, to <= version (also
+ * inside a txn).  The item walk and the classes are exactly those of crdt_diff_between_async(from,
+ * to): an item is old if it is visible at from[i] and new if it is visible at to[i].  The widths
+ * w(x) and the fields are exactly those of crdt_edits_async.  Edit p is patch p of the two-version
+ * diff: pos, del_len and ins_len are the patch's; unit is the sum of w over the new items before it
+ * (what crdt_pos_to_units would answer for pos on an encode of the text at to[i]); del_units and
+ * ins_units are the sums of w over its old-only and its new-only items; ins_off is the sum of the
+ * earlier ins_units; reserved is 0.  The pool is the encodings of the new-only items in patch order.
+ * Applied front to back to the encoded text at from[i], the edits give the encoded text at to[i].
+ * from > to is allowed; from == to gives no edits; to == version gives exactly the result of
+ * crdt_edits_async(from, enc), array for array, pool included.
+ * An index has no result, as above, when from[i] or to[i] is above the document's version, the
+ * document is poisoned, it has no content or a content stream shorter than its orders, or the sum
+ * of w over all its orders is 0xFFFFFFFF or more; the other indexes are not affected.
+ * The result is the edits result: this call replaces it under the rules of crdt_edits_async
+ * (stream-ordered, one wait inside, publishes first if needed, no duplicates in docs, enc checked,
+ * CRDT_E_NOMEM leaves the engine usable without an edits result and the same call then succeeds;
+ * it changes no document and none of the other seven results), and crdt_edits_counts,
+ * crdt_edits_read, crdt_last_edits_ms and crdt_rebase_async(CRDT_REBASE_FROM_EDITS) serve it
+ * without knowing which call made it: for the rebase, old is the text at from[i] and new is the
+ * text at to[i], in chars and in units. */
+int crdt_edits_between_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* from,
+                             const uint32_t* to, int enc);
 /* Sizes of the last edits result, per docs[i] of that call (syncs); either may be NULL. */
 int crdt_edits_counts(crdt_engine* e, uint32_t* n_edits, uint32_t* n_ins_units);
 /* Result i: edits[n_edits[i]] and ins_units[n_ins_units[i]] (uint8_t or uint16_t by the call's enc);

@@ -338,6 +338,7 @@ def lib():
     L.crdt_find_seek_dev_async.argtypes = [vp, u64, vp, vp, C.c_int, vp]
     L.crdt_last_find_ms.argtypes = [vp, P(C.c_double)]
     L.crdt_edits_async.argtypes = [vp, u64, P(u32), P(u32), C.c_int]
+    L.crdt_edits_between_async.argtypes = [vp, u64, P(u32), P(u32), P(u32), C.c_int]
     L.crdt_edits_counts.argtypes = [vp, P(u32), P(u32)]
     L.crdt_edits_read.argtypes = [vp, u64, vp, vp]
     L.crdt_last_edits_ms.argtypes = [vp, P(C.c_double)]
@@ -377,7 +378,7 @@ EXPORTED_SYMBOLS = [
     "crdt_lines_async", "crdt_line_counts", "crdt_lines_read", "crdt_pos_to_linecol", "crdt_linecol_to_pos",
     "crdt_pos_to_linecol_dev_async", "crdt_linecol_to_pos_dev_async", "crdt_last_lines_ms",
     "crdt_find_async", "crdt_find_counts", "crdt_find_read", "crdt_find_seek", "crdt_find_seek_dev_async", "crdt_last_find_ms",
-    "crdt_edits_async", "crdt_edits_counts", "crdt_edits_read", "crdt_last_edits_ms",
+    "crdt_edits_async", "crdt_edits_between_async", "crdt_edits_counts", "crdt_edits_read", "crdt_last_edits_ms",
     "crdt_rebase_async", "crdt_rebase_counts", "crdt_rebase_read", "crdt_rebase", "crdt_rebase_dev_async", "crdt_last_rebase_ms",
     "crdt_set_fused_publish", "crdt_fused_publish_stats", "crdt_debug_vpos", "crdt_debug_publish_plan",
     "crdt_set_replay_balance", "crdt_debug_balance_board", "crdt_set_window_decode", "crdt_set_balance_map",
@@ -894,6 +895,32 @@ class Engine:
                             f"document, or one without content")
         return [None if int(counts[0][i]) == 0xFFFFFFFF else self.edits_read(i, counts) for i in range(len(counts[0]))]
 
+    def edits_between_async(self, docs, from_, to, enc="utf8"):
+        """compute the edits from version from_[i] to version to[i] for docs[i] (no duplicates) on the
+        device, in units of enc; the result replaces the last edits result and is read like one
+        (edits_counts, edits_read, edits_ms, rebase_async("edits"))"""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        a = np.ascontiguousarray(from_, dtype=np.uint32)
+        b = np.ascontiguousarray(to, dtype=np.uint32)
+        if d.shape != a.shape or d.shape != b.shape or d.ndim != 1:
+            raise ValueError("edits_between: docs, from_ and to are 1-d and of equal length")
+        enc = int(self.ENCODINGS.get(enc, enc))
+        _check(self.L.crdt_edits_between_async(self.h, d.shape[0], _p(d), _p(a), _p(b), enc), "edits_between_async")
+        self._ed_n, self._ed_enc = d.shape[0], enc
+
+    def edits_between(self, docs, from_, to, enc="utf8", strict: bool = True):
+        """what edits() returns, for the edits that turn the encoded text of docs[i] at version
+        from_[i] into its encoded text at version to[i] (either may be the later one).  An index
+        without a result raises CrdtError, or is None with strict=False; the other indexes are not
+        affected."""
+        self.edits_between_async(docs, from_, to, enc)
+        counts = self.edits_counts()
+        bad = np.flatnonzero(counts[0] == 0xFFFFFFFF)
+        if strict and bad.size:
+            raise CrdtError(f"edits_between failed rc=-100 for indexes {bad.tolist()}: a version above the document's, a "
+                            f"poisoned document, or one without content")
+        return [None if int(counts[0][i]) == 0xFFFFFFFF else self.edits_read(i, counts) for i in range(len(counts[0]))]
+
     def edits_ms(self) -> float:
         """device time of the last edits call (HIP events)"""
         x = C.c_double()
@@ -1320,6 +1347,11 @@ class ListCRDT:
         """diff_since's triple for what turns the text at version `a` into the text at version `b`
         (any two versions up to version(), in either order)"""
         return self.e.diff_between([0], [a], [b])[0]
+
+    def edits_between(self, a: int, b: int, enc="utf8"):
+        """(edits [n, 8] u32, ins np.uint8 | np.uint16): what turns the encoded text at version `a`
+        into the encoded text at version `b` (Engine.edits_between; needs set_content)"""
+        return self.e.edits_between([0], [a], [b], enc)[0]
 
     def rebase_between(self, a: int, b: int, positions, dir: str = "old_to_new", bias: str = "right"):
         """(y, hit): char positions of the text at version `a` moved to where they stand in the text

@@ -19,6 +19,7 @@
 #include "lines.h"
 #include "find.h"
 #include "edits.h"
+#include "edits2.h"
 #include "rebase.h"
 
 using namespace crdt;
@@ -474,6 +475,9 @@ struct crdt_engine {
   DevBuf<Edit> ed_edits;
   DevBuf<u8> ed_units;
   u32 ed_mode = 0;
+  // crdt_edits_between_async: the versions to go to, their bitmaps and the width planes (k_ed_planes)
+  std::vector<u32> ed_to_h;
+  DevBuf<u32> ed_to, ed_bm_to, ed_planes;
   // rebase map (crdt_rebase_async): span tables copied from the diff or the edits result (rb_src),
   // at the source's per-index offsets; the unit table exists after an edits source only.  No
   // other call reads or writes these buffers, so the map outlives its source.
@@ -550,7 +554,7 @@ struct crdt_engine {
     free_bufs(diff_docs, diff_since, diff_bm_base, diff_bm, diff_pat, diff_io, diff_it, diff_to, diff_bm_to);
     free_bufs(co_docs, co_ver, co_bm_base, co_sp_base, co_bm, co_rk, co_opos, co_ord, co_text);
     free_bufs(blame_docs, blame_runs, enc_docs, enc_sp_base, enc_samples, enc_units, ln_tab, fd_pat, fd_tab);
-    free_bufs(ed_docs, ed_since, ed_bm_base, ed_bm, ed_words, ed_edits, ed_units, rb_ch, rb_un);
+    free_bufs(ed_docs, ed_since, ed_bm_base, ed_bm, ed_words, ed_edits, ed_units, ed_to, ed_bm_to, ed_planes, rb_ch, rb_un);
   }
 
   int set_device() {
@@ -1706,6 +1710,82 @@ struct crdt_engine {
     if (r) return r;
     if (!all_lds) HIPCHK(hipMemsetAsync(ed_bm.p, 0, words * 4, stream));
     return mode == ENC_UTF8 ? edits_sweeps<ENC_UTF8>(n, xw) : edits_sweeps<ENC_UTF16>(n, xw);
+  }
+
+  Ed2IO ed2_view() const { return Ed2IO{ed_view(), ed_to.p, ed_bm_to.p, ed_planes.p}; }
+  // the kernels of one edits_between call, for one encoding (after the uploads and the start event)
+  template <u32 ENC>
+  int edits2_sweeps(u64 n, u32 xw) {
+    Pools pv = pools_view(pools);
+    PubOut ov = pub_view();
+    DiffIO mark{};  // k_diff_mark reads these four only
+    mark.docs = ed_docs.p;
+    mark.since = ed_since.p;
+    mark.bm_base = ed_bm_base.p;
+    mark.bm = ed_bm.p;
+    DiffIO mark_to = mark;
+    mark_to.since = ed_to.p;
+    mark_to.bm = ed_bm_to.p;
+    hipLaunchKernelGGL(k_diff_mark, dim3((u32)n), dim3(DIFF_T), (size_t)xw * 4, stream, pv, mark, (u32)n, xw);
+    hipLaunchKernelGGL(k_diff_mark, dim3((u32)n), dim3(DIFF_T), (size_t)xw * 4, stream, pv, mark_to, (u32)n, xw);
+    hipLaunchKernelGGL(k_ed_planes<ENC>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ed2_view(), (u32)n);
+    hipLaunchKernelGGL((k_edits2<ENC, false>), dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, ed2_view(), (u32)n);
+    hipLaunchKernelGGL(k_result_scan<EdRes>, dim3(1), dim3(DIFF_SCAN_T), 0, stream, ed.res.p, (u32)n, ed.tot.p);
+    int r = ed.read_totals();
+    if (!r) r = ed_edits.grow(stream, ed.tot_h[0]);
+    if (!r) r = ed_units.grow(stream, ed.tot_h[1] * (ENC == ENC_UTF8 ? 1u : 2u));
+    if (r) return r;
+    hipLaunchKernelGGL((k_edits2<ENC, true>), dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, ed2_view(), (u32)n);
+    return ed.stop();
+  }
+  // crdt_edits_between_async: run_edits with a version on either side, as run_diff_between is
+  // run_diff's.  k_diff_mark runs twice on the edits job's buffers (from -> ed_bm, to -> ed_bm_to,
+  // the same bases), k_ed_planes indexes the widths, and k_edits2 counts and writes into the edits
+  // job's own result, which is the edits result from here on.
+  int run_edits_between(u64 n, const uint32_t* dl, const uint32_t* from, const uint32_t* to, u32 mode) {
+    int r = set_device();
+    if (r) return r;
+    ed.drop();
+    if (!published) {
+      r = publish();
+      if (r) return r;
+    }
+    ed_mode = mode;
+    r = ed.begin(n);
+    if (r) return r;
+    if (!n) {
+      ed.valid = true;
+      return 0;
+    }
+    ed_docs_h.assign(dl, dl + n);
+    ed_since_h.assign(from, from + n);
+    ed_to_h.assign(to, to + n);
+    ed_bm_h.resize(n);
+    u64 words = 0;
+    u32 xw = 0;           // the largest listed bitmap that k_diff_mark builds in LDS
+    bool all_lds = true;  // ... and every listed one is (no bitmap word needs zeroing)
+    for (u64 i = 0; i < n; i++) {
+      ed_bm_h[i] = words;
+      u32 nw = pub_words(seg_h[dl[i]].ord_cap);
+      words += nw;
+      if (nw <= DIFF_MARK_WORDS) xw = std::max(xw, nw);
+      else all_lds = false;
+    }
+    r = grow_bufs(n, ed_docs, ed_since, ed_to, ed_bm_base);
+    if (!r) r = grow_bufs(words, ed_bm, ed_bm_to);
+    if (!r) r = ed_planes.grow(stream, words * (mode == ENC_UTF8 ? 2u : 1u));
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(ed_docs.p, ed_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ed_since.p, ed_since_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ed_to.p, ed_to_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ed_bm_base.p, ed_bm_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    r = ed.start();
+    if (r) return r;
+    if (!all_lds) {
+      HIPCHK(hipMemsetAsync(ed_bm.p, 0, words * 4, stream));
+      HIPCHK(hipMemsetAsync(ed_bm_to.p, 0, words * 4, stream));
+    }
+    return mode == ENC_UTF8 ? edits2_sweeps<ENC_UTF8>(n, xw) : edits2_sweeps<ENC_UTF16>(n, xw);
   }
 
   CoIO co_view() const {
@@ -2994,7 +3074,8 @@ uint64_t crdt_mem_bytes(const crdt_engine* e) {
          buf_bytes(e->co.res, e->co_docs, e->co_ver, e->co_bm_base, e->co_sp_base, e->co_bm, e->co_rk, e->co_opos, e->co_ord, e->co_text) +
          buf_bytes(e->blame.res, e->blame_docs, e->blame_runs, e->enc.res, e->enc_docs, e->enc_sp_base, e->enc_samples, e->enc_units) +
          buf_bytes(e->ln.res, e->ln_tab, e->fd.res, e->fd_tab, e->fd_pat) +
-         buf_bytes(e->ed.res, e->ed_docs, e->ed_since, e->ed_bm_base, e->ed_bm, e->ed_words, e->ed_edits, e->ed_units) +
+         buf_bytes(e->ed.res, e->ed_docs, e->ed_since, e->ed_bm_base, e->ed_bm, e->ed_words, e->ed_edits, e->ed_units, e->ed_to, e->ed_bm_to,
+                   e->ed_planes) +
          buf_bytes(e->rb.res, e->rb_ch, e->rb_un) +
          e->n_docs * (sizeof(DocState) + sizeof(DocSeg) + 4 + 4 + 8);
 }
@@ -3130,6 +3211,16 @@ int crdt_edits_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, cons
   return oom_as_nomem([&] { return e->run_edits(n_docs, docs, since, (u32)enc); });
 }
 
+int crdt_edits_between_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* from, const uint32_t* to, int enc) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n_docs && (!docs || !from || !to)) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
+  if (enc != CRDT_ENC_UTF8 && enc != CRDT_ENC_UTF16) {
+    g_last_error = "edits_between: enc is CRDT_ENC_UTF8 or CRDT_ENC_UTF16";
+    return CRDT_E_ARG;
+  }
+  return oom_as_nomem([&] { return e->run_edits_between(n_docs, docs, from, to, (u32)enc); });
+}
+
 int crdt_edits_counts(crdt_engine* e, uint32_t* n_edits, uint32_t* n_ins_units) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e)) return CRDT_E_ARG;
@@ -3152,7 +3243,7 @@ int crdt_edits_read(crdt_engine* e, uint64_t i, crdt_edit* edits, void* ins_unit
   if (i >= e->ed.n) return CRDT_E_ARG;
   const EdRes& x = e->ed.res_h[i];
   if (x.flags & ED_BAD) {
-    g_last_error = "edits: since above the document's version, a poisoned document, or one without content (or with too short a stream)";
+    g_last_error = "edits: a version above the document's, a poisoned document, or one without content (or with too short a stream)";
     return CRDT_E_ARG;
   }
   u64 usz = e->ed_mode == ENC_UTF8 ? 1u : 2u;
