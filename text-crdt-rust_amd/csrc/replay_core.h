@@ -696,6 +696,18 @@ struct Replayer {
     c = Cursor{lf, (u32)idx, order - start};
     return true;
   }
+  // A cursor carried from one delete of a run to the next (fast_deletes) names the place that a
+  // lookup of the next target's order finds, in a visible entry: checked in the CPU emulation only.
+  CRDT_HD void carried_is_found(u32 order, const Cursor& c) {
+#ifdef CRDT_EMU_CHECKS
+    Cursor f{INVALID, INVALID, INVALID};
+    bool ok = find_order(order, true, f);
+    CRDT_EXPECT(ok && f.leaf == g(C_LEAF) && c.leaf == f.leaf && c.idx == f.idx && c.off == f.off);
+    CRDT_EXPECT(w.cget_len(c.idx) > (i32)c.off);
+#else
+    (void)order; (void)c;
+#endif
+  }
   // doc.rs:121-136 get_cursor_after
   CRDT_HD bool cursor_after(u32 order, bool load, Cursor& c) {
     if (order == ROOT_ORDER) {
@@ -1795,6 +1807,7 @@ struct Replayer {
         }
       }
     }
+    CRDT_STAT(74, pre);
     if (n + m > (u32)L) return 0;
     // entry writes straight to the cache; the visible count drops by exactly the l deleted items
     w.cset(idx, ha ? pa : dd);
@@ -1844,25 +1857,24 @@ struct Replayer {
       k = k < off ? k : off;  // E keeps its first item (deleting it is a different shape)
       k = k < kmax ? k : kmax;
       if (k < 2u) return 0;
-      if (mid) {
-        Span pc = truncate(E, off + 1u);  // (E's visible items stay in E + pc)
-        w.cache_shift_right(idx + 1u, n, 1u);
-        w.cset(idx + 1u, pc);
-        n += 1u;
-        inc(S_N_ENTRIES, 1u);
-      }
+      CRDT_STAT(63, p0);
       delta = p0 ? k / 2u : (k + 1u) / 2u;  // new entries F_1..F_delta, newest first after E
-      w.cache_shift_right(idx + 1u, n, delta);
-      w.cset_lanes(idx + 1u, idx + 1u + delta, [&](u32 lane) {
-        u32 q = delta - (lane - idx - 1u);           // F_q
+      // one shift makes room for F_1..F_delta and, mid-entry, for pc = E[off+1..] behind them
+      // (E's visible items stay in E + pc); one lane-parallel write places them all
+      u32 pl = idx + 1u + delta;  // pc's lane (mid)
+      u32 rest = (u32)E.len - off - 1u;
+      w.cache_shift_right(idx + 1u, n, delta + mid);
+      w.cset_lanes(idx + 1u, pl + mid, [&](u32 lane) {
+        u32 q = pl - lane;                           // F_q
         u32 jc = p0 ? 2u * q : 2u * q - 1u;          // the op (1-based) that created it
         u32 tc = t1 - (jc - 1u);
         u32 two = jc + 1u <= k ? 1u : 0u;  // {tc-1, tc-1, orr, -2} or {tc, tc-1, orr, -1}: arithmetic, no selects
-        return Span{tc - two, tc - 1u, orr, (i32)~two};
+        u32 isp = lane == pl ? 1u : 0u;    // (written only when mid)
+        return Span{isp ? t1 + 1u : tc - two, isp ? t1 : tc - 1u, orr, isp ? (i32)rest : (i32)~two};
       });
       if (p0) w.cset(idx + 1u + delta, Span{t1, N0.ol, N0.orr, N0.len - 1});
-      E.len = (i32)(off + 1u - k);
-      w.cset(idx, E);
+      w.cset_len(idx, (i32)(off + 1u - k));  // (only E's len changed)
+      delta += mid;
     } else {
       u32 ha = off > 0u;
       if (has_nx && can_append_u(Span{t1 + 1u, t1, orr, E.len - (i32)off - 1}, N0)) return 0;
@@ -1873,12 +1885,14 @@ struct Replayer {
       u32 cnt = ha + k + (rest != 0u);
       delta = cnt - 1u;
       w.cache_shift_right(idx + 1u, n, delta);
+      // lane idx keeps E's order and origin_left (E[..off], or deleted item 0 when off == 0);
+      // every later piece starts at t1 + j with the item before it as its origin_left
+      i32 len0 = ha ? (i32)off : -1;
       w.cset_lanes(idx, idx + cnt, [&](u32 lane) {
-        u32 p = lane - idx;
-        u32 j = p - ha;  // deleted item j (0-based), or the remainder when j == k
-        if (ha && p == 0u) return Span{E.order, E.ol, orr, (i32)off};
-        if (j < k) return Span{t1 + j, (j == 0u && !ha) ? E.ol : t1 + j - 1u, orr, -1};
-        return Span{t1 + k, t1 + k - 1u, orr, (i32)rest};
+        u32 j = lane - idx - ha;  // deleted item j (0-based), or the remainder when j == k
+        bool head = lane == idx;
+        u32 o = head ? E.order : t1 + j;
+        return Span{o, head ? E.ol : o - 1u, orr, head ? len0 : (j < k ? -1 : (i32)rest)};
       });
     }
     p(C_N, n + delta);
@@ -1989,7 +2003,7 @@ struct Replayer {
     // The leaf ran out of room (or the run reached a shape the segment does not take): the next
     // delete goes the general way -- mutate_entry + insert_internal, splitting the leaf -- and the
     // rest of the run continues from wherever its next target now lives.
-    CRDT_STAT(9, 1); CRDT_STAT(12, k); CRDT_STAT(13, split_first);
+    CRDT_STAT(9, 1); CRDT_STAT(12, k); CRDT_STAT(13, split_first); CRDT_STAT(68, k > 64u);
 #ifdef CRDT_PROF_LOOP
     u32 lp_gen = 0, lp_split = 0, lp_find = 0, lp_seg = 0;
 #endif
@@ -1999,10 +2013,11 @@ struct Replayer {
 #endif
       CRDT_STAT(10, 1);
       if (g(K_LEAF) - g(S_N_LEAVES) < 2u) break;
+      // (idx, off) is the next target's place: the call's own cursor, or where the segment before
+      // left it (delete_segment) -- no lookup
       Cursor c{g(C_LEAF), idx, off};
-      if (done != 0u) {
-        if (!find_order(back ? t1 - done : t1 + done, true, c)) break;
-      }
+      CRDT_STAT(59, done != 0u);
+      carried_is_found(back ? t1 - done : t1 + done, c);
       i32 el = w.cget_len(c.idx);
       if (el <= 0) break;
       if (c.off + l > (u32)el) break;
@@ -2011,9 +2026,50 @@ struct Replayer {
         p(C_NOW, g(C_NOW) - 1u);
         p(C_DIRTY, 1u);
         done++;
+        CRDT_STAT(62, 1);
+        CRDT_EXPECT(done == k);  // (it was the entry's first item, where a backspace run ends: k <= off + 1)
         continue;
       }
       CRDT_STAT(back ? 48 : 49, 1); CRDT_STAT(52, c.off == 0u);
+      // A delete that overflows the leaf where the split keeps the cursor's entry in the cached
+      // leaf (split index < L/2) and no piece prepends onto the next entry: insert_internal splits
+      // at idx + 1 and places the pieces there, which is what the segment writes into the leaf the
+      // split leaves behind -- so split first and let the segment take this delete with the rest
+      // of the run.  A prepend changes the entry that moves (declined), and a backspace run long
+      // enough for whole cycles keeps the general delete, whose result back_cycles recognises.
+      if ((c.idx + 1u < (u32)L / 2u) & (l == 1u)) {
+        u32 n = g(C_N), ci = c.idx + 1u;
+        u32 m = (c.off > 0u ? 1u : 0u) + (c.off + 1u < (u32)el ? 1u : 0u);
+        u32 cycles = back & (k - done - 1u >= 2u * ((u32)L - ci) ? 1u : 0u);
+        if ((n + m > (u32)L) & (cycles ^ 1u)) {
+          u32 pre = 0;
+          if (ci < n) {  // (m != 0: the leaf overflows)
+            Span e = w.cget(c.idx);
+            u32 t = e.order + c.off;
+            Span last = c.off + 1u < (u32)el ? Span{t + 1u, t, e.orr, el - (i32)(c.off + 1u)}
+                                             : Span{t, c.off > 0u ? t - 1u : e.ol, e.orr, -1};
+            pre = can_append_u(last, w.cget(ci)) ? 1u : 0u;
+          }
+          CRDT_STAT(73, pre);
+          if (!pre) {
+            CRDT_STAT(61, 1);
+#ifdef CRDT_PROF_LOOP
+            prof_split = 0;
+#endif
+            split_at(ci, 0u);
+            u32 dseg = delete_segment(c.idx, c.off, back ? t1 - done : t1 + done, k - done, back, l);
+            CRDT_EXPECT(dseg != 0u);
+#ifdef CRDT_PROF_LOOP
+            lp_split += prof_split;
+            lp_seg += (u32)(w.clock() - q0) - prof_split;
+#endif
+            done += dseg;
+            idx = c.idx;
+            off = c.off;
+            continue;
+          }
+        }
+      }
 #ifdef CRDT_PROF_LOOP
       u64 q1 = w.clock();
       prof_split = 0;
@@ -2028,13 +2084,29 @@ struct Replayer {
       done++;
       if (done == k) break;
       u32 t2 = back ? t1 - done : t1 + done;
-      // (backspacing from inside an entry: the item before the deleted one ends the entry's first
-      // part, which stays at its index of the cached leaf -- no lookup)
-      if (back & (c.off != 0u)) c.off -= 1u;
-      else if (!find_order(t2, true, c)) break;
-      el = w.cget_len(c.idx);
-      if (el <= 0) break;
-      if (c.off + l > (u32)el) break;
+      // Where the run goes on follows from the delete just made.  Backspacing from inside an entry:
+      // the item before the deleted one ends the entry's first part, which stays at its index of
+      // the cached leaf.  Forward: item 0 of the remainder (or of the entry it prepended onto), one
+      // entry behind the deleted piece: at idx + 1 (+ 1 behind a first part) where the cached leaf
+      // stayed, behind the pieces that lead the new leaf where the split made that the cached one.
+      // An order is looked up only where that entry left the cached leaf (the remainder prepended
+      // onto an entry that a split moved away: the index is the leaf's end) or the run left its
+      // entry (backspace at off == 0).
+      u32 nxt = (c.off != 0u ? 1u : 0u) + (g(C_LEAF) != c.leaf ? 0u : c.idx + 1u);
+      if (back & (c.off != 0u)) {
+        c.off -= 1u;
+        CRDT_STAT(59, 1);
+      } else if ((back ^ 1u) & (nxt < g(C_N))) {
+        c = Cursor{g(C_LEAF), nxt, 0u};
+        CRDT_STAT(59, 1);
+      } else {
+        CRDT_STAT(75, 1);
+        if (!find_order(t2, true, c)) break;
+        el = w.cget_len(c.idx);
+        if (el <= 0) break;
+        if (c.off + l > (u32)el) break;
+      }
+      carried_is_found(t2, c);
 #ifdef CRDT_PROF_LOOP
       u64 q3 = w.clock();
       lp_find += (u32)(q3 - q2);
@@ -2056,6 +2128,8 @@ struct Replayer {
 #endif
       CRDT_STAT(53, dseg); CRDT_STAT(54, dseg == 0u);
       done += dseg;
+      idx = c.idx;  // (the segment moved the cursor on)
+      off = c.off;
     }
 #ifdef CRDT_PROF
     u64 pt3 = w.clock();
@@ -2090,8 +2164,11 @@ struct Replayer {
     return done * per;
   }
   // Up to k one-item deletes of a run (the first at `off` of entry idx, target t), in closed form
-  // or op by op, while the leaf has room.  Returns the deletes applied.
-  CRDT_HD u32 delete_segment(u32 idx, u32 off, u32 t, u32 k, u32 back, u32 l) {
+  // or op by op, while the leaf has room.  Returns the deletes applied, and moves (idx, off) to
+  // the place of the run's next target in the cached leaf, which follows from the deletes applied:
+  // a backspace run goes on at E's new last item, a forward run at item 0 of the remainder, which
+  // sits behind E's first part (off > 0) and the deleted items (meaningless once the run is over).
+  CRDT_HD u32 delete_segment(u32& idx, u32& off, u32 t, u32 k, u32 back, u32 l) {
     u32 done = k >= 2u ? delete_run_closed(idx, off, t, k, back) : 0u;
     CRDT_STAT(11, done); CRDT_STAT(14, 1);
     if (done == 0u) {  // op by op
@@ -2104,6 +2181,12 @@ struct Replayer {
         if (!leaf_delete(ij, oj, l)) break;
         done++;
       }
+    }
+    if (back) {
+      off -= done;
+    } else if (done) {
+      idx += (off > 0u) + done;
+      off = 0u;
     }
     return done;
   }
@@ -2151,6 +2234,7 @@ struct Replayer {
     p(C_DIRTY, 1u);
     (void)pre_vis;
     CRDT_STAT(50, m == 0u);
+    CRDT_STAT(65, pre);
     if (m == 0u) return;
     inc(S_N_ENTRIES, m);
     u32 ci = idx + 1u;
@@ -2187,6 +2271,7 @@ struct Replayer {
         at = 0u;
       } else {
         p(C_N, ci + m);
+        CRDT_STAT(64, pre);
       }
     } else {
       CRDT_STAT(51, 1);
@@ -2474,6 +2559,7 @@ struct Replayer {
           if (!seq_to_order(agent, r.w3, orr)) return 0;
         }
       }
+      CRDT_STAT(60, ins ^ 1u);  // (a delete run's entry point: the lookup that stays)
       if (!find_order(ol, true, c)) return 0;  // doc.rs:101-136 (loads the item's leaf)
       c.off += ins;                             // get_cursor_after
     } else if (remote) {
