@@ -6,6 +6,8 @@ concurrent_wire: several agents editing their own replicas (oracle) and exchangi
 returns one causally ordered wire batch that replays the whole history.
 gossip_log / causal_shuffle / gossip_family: partially delivered concurrent histories (every agent
 pulls from one peer at a time) and seeded causal reorderings of them.
+multi_op_wire / multi_op_family: concurrent_wire's scheme with local txns of 1..4 ops (replaces,
+typing on, deletes inside the txn's own insert): multi-op remote txns in a concurrent history.
 """
 import bisect
 import functools
@@ -164,6 +166,136 @@ def concurrent_wire(seed: int, n_agents: int = 3, rounds: int = 6, ops_per_round
                 return build_wire(history), len(history)
             seen[i] = len(history)
     return build_wire(history), len(history)
+
+
+MULTI_OP_KINDS = ("replace", "delete", "insert", "typing_on", "delete_inside")
+MULTI_OP_WEIGHTS = (0.2, 0.15, 0.25, 0.25, 0.15)
+
+
+def draw_multi_op_txn(rng, n: int, end_ok: bool = False):
+    """One local txn of 1..4 LocalOps (pos, del, ins) on a text of `n` items, each op drawn against
+    the length the ops before it leave.  Kinds (MULTI_OP_KINDS, drawn with MULTI_OP_WEIGHTS):
+    a replace (delete 1..3 and insert 1..3 at one position), a plain delete of 1..4, a plain insert
+    of 1..3, typing on (an insert directly after the txn's previous insert: its origin_left is an
+    item of its own txn) and a delete inside the txn's previous insert (its target is an item of
+    its own txn).  A kind that cannot be drawn (no previous insert, too short a text) falls back
+    to a plain insert.  Unless `end_ok`, nothing is inserted after the text's last item and no
+    delete leaves fewer than 2 items (gossip_log's ERR_NONTERMINATING restriction).
+    Returns (ops, the text's length after them)."""
+    ops = []
+    last = None  # (pos, len) of the txn's previous insert, in the text as it is now
+    hi = 0 if end_ok else 1  # inserts land in [0, n - hi]
+    for _ in range(rng.randint(1, 4)):
+        kind = rng.choices(MULTI_OP_KINDS, MULTI_OP_WEIGHTS)[0]
+        op = None
+        if kind == "replace" and n - hi >= 2 and n >= 3:
+            d = rng.randint(1, min(3, n - hi - 1, n - 2))
+            p = rng.randint(0, n - hi - d)
+            i = rng.randint(1, 3)
+            op, new_last = (p, d, i), (p, i)
+        elif kind == "delete" and n >= 3:
+            p = rng.randint(0, n - 2)
+            d = rng.randint(1, min(4, n - p, n - 2))
+            op = (p, d, 0)
+            if last is None or p >= last[0] + last[1]:
+                new_last = last
+            elif p + d <= last[0]:
+                new_last = (last[0] - d, last[1])
+            else:
+                new_last = None
+        elif kind == "typing_on" and last is not None and last[0] + last[1] <= n - hi:
+            i = rng.randint(1, 3)
+            op, new_last = (last[0] + last[1], 0, i), (last[0], last[1] + i)
+        elif kind == "delete_inside" and last is not None and n >= 3:
+            p = rng.randint(last[0], last[0] + last[1] - 1)
+            d = rng.randint(1, min(2, last[0] + last[1] - p, n - 2))
+            op, new_last = (p, d, 0), ((last[0], last[1] - d) if last[1] > d else None)
+        if op is None:  # a plain insert, also the fall-back
+            p = rng.randint(0, max(n - hi, 0))
+            i = rng.randint(1, 3)
+            op, new_last = (p, 0, i), (p, i)
+        ops.append(op)
+        n += op[2] - op[1]
+        last = new_last
+    return ops, n
+
+
+def multi_op_wire(seed: int, n_agents: int = 3, rounds: int = 6, txns_per_round: int = 3, base_len: int = 20,
+                  leaf: int = 32):
+    """concurrent_wire's scheme with multi-op txns: every agent edits an oracle replica of its own
+    (layout `leaf`), each local txn is draw_multi_op_txn's 1..4 LocalOps recorded through the
+    oracle's local->remote recorder as ONE remote txn (a replace, a delete the recorder splits at a
+    client_with_order run boundary and every further LocalOp add wire ops), delivery within a round
+    is shuffled but keeps each agent's order, and at the end of a round everyone merges.  The
+    history is truncated where a merge fails.  So the remote txns insert and delete, insert twice,
+    name items their own earlier ops created and delete parts of their own inserts -- the shapes
+    only apply_txn's interpreter replays -- in a history whose frontier has several heads.
+    Returns (wire, n_txns) like concurrent_wire."""
+    from oracle_lib import OracleDoc, lib, _p
+    import ctypes as C
+    rng = random.Random(seed)
+    L = lib()
+    names = [f"m{chr(97 + i)}{rng.randrange(1 << 12):03x}" for i in range(n_agents)]
+    buf = C.create_string_buffer(1 << 16)
+
+    def record(doc, agent_id, ops):
+        c = np.array([len(ops)], np.uint32)
+        p = np.array(ops, np.uint32).reshape(-1, 3)
+        n = L.orc_local_trace_to_wire(doc.h, agent_id, 1, _p(c), _p(p), C.cast(buf, C.c_void_p), 1 << 16)
+        return None if n < 0 else parse_wire(buf.raw[:n])[1]
+
+    reps = [OracleDoc(leaf, 16 if leaf == 32 else 8) for _ in range(n_agents)]
+    ids = [reps[i].agent(names[i]) for i in range(n_agents)]
+    history = record(reps[0], ids[0], [(0, 0, base_len)])
+    for i in range(1, n_agents):
+        if reps[i].apply_remote_wire(build_wire(history)) != 0:
+            return build_wire(history), len(history)
+    for _ in range(rounds):
+        snapshot = len(history)
+        per = {}
+        for i in range(n_agents):
+            for _ in range(txns_per_round):
+                ops, _n = draw_multi_op_txn(rng, len(reps[i]))
+                t = record(reps[i], ids[i], ops)
+                if t is None:
+                    break
+                per.setdefault(i, []).append(t)
+        while any(per.values()):  # a shuffled interleaving that keeps each agent's order
+            i = rng.choice([k for k, v in per.items() if v])
+            history += per[i].pop(0)
+        for i in range(n_agents):
+            others = [t for t in history[snapshot:] if t[0] != names[i]]
+            if others and reps[i].apply_remote_wire(build_wire(others)) != 0:
+                return build_wire(history), len(history)
+    return build_wire(history), len(history)
+
+
+# the committed histories of tests/test_multi_op_ref.py, tests/test_gpu_multi_op.py: per seed
+# (n_agents, rounds)
+MULTI_OP_SEEDS = range(40)
+
+
+def multi_op_params(seed: int) -> dict:
+    return dict(n_agents=2 + seed % 4, rounds=4 + seed % 3)
+
+
+@functools.lru_cache(maxsize=None)
+def multi_op_family():
+    """[(seed, wire)] of the committed multi-op histories; generated once per process"""
+    return [(s, multi_op_wire(s, **multi_op_params(s))[0]) for s in MULTI_OP_SEEDS]
+
+
+def txn_shape(t):
+    """shape flags of one parsed remote txn: (mixed, two_inserts, own_origin inserts, own_target
+    deletes, five_ops) -- an own origin / target is an id of the txn's author inside the txn's own
+    seq range"""
+    a, s, _ps, ops = t
+    end = s + sum(op[5] for op in ops)
+    n_ins = sum(op[0] == 0 for op in ops)
+    own_o = sum(1 for k, an, asq, bn, bsq, _ln in ops
+                if k == 0 and ((an == a and s <= asq < end) or (bn == a and s <= bsq < end)))
+    own_t = sum(1 for k, an, asq, _bn, _bsq, ln in ops if k != 0 and an == a and asq < end and asq + ln > s)
+    return (0 < n_ins < len(ops), n_ins >= 2, own_o, own_t, len(ops) >= 5)
 
 
 def config5_wire(seed: int, base_len: int = 4096, n_agents: int = 16, rounds: int = 8, ops: int = 4,

@@ -393,6 +393,7 @@ struct Replayer {
   // The record at pos without moving the window (general path: from HBM when outside it).
   CRDT_HD Rec rec_at(u32 pos) const {
     u32 d = pos - g(T_RB_BASE);
+    CRDT_STAT(78, d < 64u); CRDT_STAT(79, d >= 64u);
     return d < 64u ? w.rec_get(d) : w.ld_rec(w.at(recs(), pos));
   }
 
@@ -2914,6 +2915,7 @@ struct Replayer {
         else if (prof_cat == 2u) inc(S_PROF2, dt);
         else inc(S_PROF3, dt);
 #endif
+        CRDT_STAT(76, fast != 0u && kind == REC_RTXN); CRDT_STAT(77, kind == REC_RTXN ? fast / 3u : 0u);  // (general-form runs at stride 3)
         if (fast) {
           if (g(F_GEN)) inc(S_GEN_DONE);
           else pos += fast;
