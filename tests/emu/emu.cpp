@@ -296,6 +296,23 @@ int emu_run_local(void* h, uint16_t agent, uint32_t ntxn, const uint32_t* counts
   return d->run();
 }
 
+// Local txns by several agents of the document (interned before, emu_agent), one agent per txn, as
+// one stream on a fresh emulated document.
+int emu_run_local_agents(void* h, uint32_t ntxn, const uint32_t* agents, const uint32_t* counts, const uint32_t* patches3,
+                         uint32_t leaf_div) {
+  EmuDoc* d = (EmuDoc*)h;
+  StreamNeeds nd;
+  d->recs.clear();
+  const uint32_t* p = patches3;
+  for (uint32_t t = 0; t < ntxn; t++) {
+    if (agents[t] >= d->agents.names.size()) return ST_BAD_INPUT;
+    encode_local_txn(d->recs, nd, agents[t], p, counts[t]);
+    p += 3 * counts[t];
+  }
+  d->prepare(nd, false, leaf_div);  // (untracked, as emu_run_local and the engine's local-only documents)
+  return d->run();
+}
+
 // local trace with a PROBE record after every txn; answers4 gets (agent, seq, pos, deleted)
 int emu_run_local_probed(void* h, uint16_t agent, uint32_t ntxn, const uint32_t* counts, const uint32_t* patches3,
                          const uint32_t* probes3, uint32_t* answers4, uint32_t leaf_div) {

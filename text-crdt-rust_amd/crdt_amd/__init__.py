@@ -458,8 +458,8 @@ class Engine:
                 np.array(txns, np.uint32).reshape(-1, 2),
                 np.concatenate(ops).astype(np.uint32) if ops else np.zeros((0, 3), np.uint32))
 
-    def apply_local(self, per_doc) -> np.ndarray:
-        return self.apply_local_arrays(*self._local_arrays(per_doc))
+    def apply_local(self, per_doc, stage_only: bool = False) -> np.ndarray:
+        return self.apply_local_arrays(*self._local_arrays(per_doc), stage_only=stage_only)
 
     def apply_local_probed(self, d, off, tx, ops, probes):
         """apply_local_arrays with one probe (pos, agent, seq) after every txn; returns (status,
@@ -476,13 +476,17 @@ class Engine:
                "apply_local_probed")
         return st, ans
 
-    def apply_local_arrays(self, d, off, tx, ops) -> np.ndarray:
+    def apply_local_arrays(self, d, off, tx, ops, stage_only: bool = False) -> np.ndarray:
         """crdt_apply_local on CSR arrays: docs [n], txn_off [n+1] (u64), txns [T,2] (agent, n_ops),
-        ops [sum n_ops, 3] (pos, del, ins)."""
+        ops [sum n_ops, 3] (pos, del, ins).  stage_only: crdt_stage_local (run() replays it)."""
         d = np.ascontiguousarray(d, dtype=np.uint32)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         tx = np.ascontiguousarray(tx, dtype=np.uint32).reshape(-1, 2)
         ops = np.ascontiguousarray(ops, dtype=np.uint32).reshape(-1, 3)
+        if stage_only:
+            _check(self.L.crdt_stage_local(self.h, d.shape[0], _p(d), _p(off, C.c_uint64), tx.ctypes.data, ops.ctypes.data),
+                   "stage_local")
+            return np.zeros(d.shape[0], np.int32)
         st = np.zeros(d.shape[0], np.int32)
         _check(self.L.crdt_apply_local(self.h, d.shape[0], _p(d), _p(off, C.c_uint64), tx.ctypes.data,
                                        ops.ctypes.data, _p(st, C.c_int32)), "apply_local")

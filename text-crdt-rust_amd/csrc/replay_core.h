@@ -1758,11 +1758,13 @@ struct Replayer {
       u32 n = rn - last < 64u ? rn - last : 64u;
       u32 t2, l0;
       u32 n2 = w.typing_scan_at(w.at(recs(), last), n, remote, cpt, agent, ow1, o.w3, t2, l0);
+      CRDT_STAT(80, 1);
       end = last + n;
       if (n2 <= 1u) break;
       total += t2 - l0;
       nt += n2 - 1u;
     }
+    CRDT_STAT(86, nt > 1u); CRDT_STAT(87, nt > 1u ? nt : 0u);
     return nt;
   }
   CRDT_HD u32 fast_typing(u32 b0, u32 nv, u32 remote, u32 idx, u32 orr, u32 agent, const Rec& o, u32 first) {
@@ -1981,6 +1983,7 @@ struct Replayer {
             u32 last = pos0 + (k - 1u) * per;
             u32 n = rn - last < 64u ? rn - last : 64u;
             u32 n2 = w.delete_scan_at(w.at(recs(), last), n, remote, cpt, agent, delta);
+            CRDT_STAT(81, 1);
             end = last + n;
             if (n2 <= 1u) break;
             k += n2 - 1u;
@@ -2005,6 +2008,7 @@ struct Replayer {
     // delete goes the general way -- mutate_entry + insert_internal, splitting the leaf -- and the
     // rest of the run continues from wherever its next target now lives.
     CRDT_STAT(9, 1); CRDT_STAT(12, k); CRDT_STAT(13, split_first); CRDT_STAT(68, k > 64u);
+    CRDT_STAT(88, k > 1u); CRDT_STAT(89, k > 1u ? k : 0u);
 #ifdef CRDT_PROF_LOOP
     u32 lp_gen = 0, lp_split = 0, lp_find = 0, lp_seg = 0;
 #endif
@@ -2453,6 +2457,7 @@ struct Replayer {
     p(C_NOW, g(C_NOW) - l);
     p(C_DIRTY, 1u);
     fast_txn_commit(first, l);
+    CRDT_STAT(84, 1); CRDT_STAT(91, d_pre); CRDT_STAT(92, c_pre);
     return 1;
   }
   // A local delete of l visible items at pos that leaf_delete_span could not place in the cached
@@ -2468,6 +2473,7 @@ struct Replayer {
   // having changed nothing, when that room is not there or the range is past the document's end
   // (the general path then reports it).
   CRDT_HD u32 local_delete_pieces(u32 pos, u32 l, u32 first) {
+    CRDT_STAT(85, 1);
     if ((u64)pos + l > cur_len()) return 0;
     if (g(K_LEAF) - g(S_N_LEAVES) < 2u) return 0;
     if (g(K_DEL) - g(S_N_DEL) < l) return 0;
@@ -2663,6 +2669,7 @@ struct Replayer {
           // 96-121) is entry 0 of the emptied leaf: the front run it starts refills it
           if (front & cpt) {
             u32 kf = w.front_scan(b0, nv, agent, l);
+            CRDT_STAT(83, 1); CRDT_STAT(82, kf > 1u); CRDT_STAT(90, kf > 1u ? kf : 0u);
             if (kf > 1u) return (1u + leaf_insert_front(first, l, kf - 1u)) * per;
           }
           return per;
@@ -2677,6 +2684,7 @@ struct Replayer {
       u32 nt = typing_run(b0, nv, remote, agent, (agent & 0xFFFFu) | (o.w1 & 0xFFFF0000u), o, total);
       item.len = (i32)total;
       u32 kf = (front & cpt) && nt == 1u ? w.front_scan(b0, nv, agent, l) : 1u;
+      CRDT_STAT(82, kf > 1u); CRDT_STAT(90, kf > 1u ? kf : 0u);
       if (front) {  // (a front run commits itself; with kf > 1, nt == 1)
         u32 r = leaf_insert_front(item.orr, total, kf);
         return r ? (nt + r - 1u) * per : 0u;
