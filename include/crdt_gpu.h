@@ -225,6 +225,49 @@ int crdt_diff_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const
  * document. */
 int crdt_diff_between_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* from,
                             const uint32_t* to);
+/* Causal versions.  Orders are assigned in application order, so a version "everything with order
+ * < v" means something on this replica only; what peers exchange is a version vector.  A version
+ * vector of document d is vv[a] for the document's agent ids a = 0 .. n_agents - 1 (crdt_agent_intern;
+ * mapping names to ids across replicas is the caller's).  The version it names is the set S of
+ * orders x whose id (agent, seq) has seq < vv[agent]: delete ops as well as insert items, a delete
+ * op's orders being in client_with_order too.  An item with order x is visible at S if x is in S
+ * and no delete-log entry (key, target, len) covers x with its delete order key + (x - target) in
+ * S.  S is taken as a set: nothing requires it to be causally closed ("now minus one txn" is a
+ * legitimate version), and whether it is closed is reported (crdt_diff_vv_closed).  Entries beyond
+ * a vector's length count as 0.  Every order-prefix version is such a set: an agent's seqs are
+ * applied in seq order, so the orders below v hold a seq prefix of every agent.
+ *
+ * The vector of the order prefix version[q] of doc[q] (version == NULL: now), n_agents(doc[q])
+ * entries written at vv_out[vv_off[q]]; vv_off has n + 1 ascending entries, and slot q is
+ * vv_off[q] .. vv_off[q + 1].  CRDT_E_ARG if a slot is smaller than the document's agent count, a
+ * version is above the document's, or a document is poisoned.  Computed on the device (syncs). */
+int crdt_version_vector(crdt_engine* e, uint64_t n, const uint32_t* doc, const uint32_t* version,
+                        const uint64_t* vv_off, uint32_t* vv_out);
+/* The same on device arrays, stream-ordered and without checks on the host: a query that has no
+ * answer (see above) fills its slot with 0xFFFFFFFF. */
+int crdt_version_vector_dev_async(crdt_engine* e, uint64_t n, const uint32_t* doc, const uint32_t* version,
+                                  const uint64_t* vv_off, uint32_t* vv_out);
+/* The patches between two causal versions of docs[i]: the vectors from_vv[vv_off[i] .. vv_off[i+1])
+ * and to_vv[vv_off[i] .. vv_off[i+1]), the same layout on both sides (vv_off has n_docs + 1
+ * ascending entries).  The walk, the classes, the patches, pos, ins_off and the inserted-item
+ * arrays are exactly those of crdt_diff_between_async, with "visible at from[i] / to[i]" replaced
+ * by "visible at S_from / S_to" as defined above; on the vectors of two order prefixes
+ * (crdt_version_vector) the result is that of crdt_diff_between_async on the prefixes, array for
+ * array.
+ * The result is the diff result: this call replaces it under the rules of crdt_diff_async
+ * (stream-ordered, one wait inside, publishes first if needed, no duplicates in docs, CRDT_E_NOMEM
+ * leaves the engine usable without a diff result), and crdt_diff_counts, crdt_diff_read,
+ * crdt_last_diff_ms and crdt_rebase_async(CRDT_REBASE_FROM_DIFF) serve it without knowing which
+ * call made it.  An index with a vector longer than the document's agent count or an entry above
+ * that agent's next seq, or whose document is poisoned, has no result; the other indexes are not
+ * affected.  Does not change any document. */
+int crdt_diff_vv_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint64_t* vv_off,
+                       const uint32_t* from_vv, const uint32_t* to_vv);
+/* One byte per index of the last crdt_diff_vv_async and side (either may be NULL; syncs): 1 if the
+ * side's S is causally closed -- every txn with at least one order in S has all its parents but
+ * ROOT in S, and S holds a prefix of every txn it touches -- else 0 (also for an index without a
+ * result).  CRDT_E_ARG if the last diff result was not made by crdt_diff_vv_async. */
+int crdt_diff_vv_closed(crdt_engine* e, uint8_t* closed_from, uint8_t* closed_to);
 /* Sizes of the last diff, per docs[i] of that call (syncs).  An index whose since[i] is above the
  * document's version, or whose document is poisoned, has no result: both sizes are 0xFFFFFFFF and
  * crdt_diff_read of it returns CRDT_E_ARG; the other indexes are not affected. */
@@ -731,6 +774,10 @@ int crdt_device_bytes(uint64_t* current, uint64_t* peak, int reset_peak);
 // out of memory (k < 0: never).  A relayout that fails part-way poisons its engine: every later
 // call but crdt_engine_destroy / crdt_docs_alloc returns CRDT_E_NOMEM.
 int crdt_test_fail_alloc_after(long long k);
+// Test hook: the LDS budget, in 32-bit words, that crdt_diff_vv_async launches its mark kernel with
+// (the default and the maximum: 16,384).  A document whose two bitmaps do not fit the budget takes
+// the path that builds them in device memory, so a small budget sends small documents there.
+int crdt_test_set_vv_lds_words(uint32_t words);
 // Config 1's per-op check: after txn t (of every listed document), ask pos_to_loc(probes[t].pos)
 // and loc_to_pos(probes[t].agent, probes[t].seq) on the state reached so far (the README's two
 // mappings, cursor.rs:147-190 count_pos; answers as crdt_pos_to_loc / crdt_loc_to_pos).

@@ -299,6 +299,11 @@ def lib():
     L.crdt_doc_version.argtypes = [vp, u64, P(u32), P(u32)]
     L.crdt_diff_async.argtypes = [vp, u64, P(u32), P(u32)]
     L.crdt_diff_between_async.argtypes = [vp, u64, P(u32), P(u32), P(u32)]
+    L.crdt_version_vector.argtypes = [vp, u64, P(u32), P(u32), P(u64), P(u32)]
+    L.crdt_version_vector_dev_async.argtypes = [vp, u64, vp, vp, vp, vp]
+    L.crdt_diff_vv_async.argtypes = [vp, u64, P(u32), P(u64), P(u32), P(u32)]
+    L.crdt_diff_vv_closed.argtypes = [vp, P(C.c_uint8), P(C.c_uint8)]
+    L.crdt_test_set_vv_lds_words.argtypes = [u32]
     L.crdt_diff_counts.argtypes = [vp, P(u32), P(u32)]
     L.crdt_diff_read.argtypes = [vp, u64, vp, P(u32), P(u32)]
     L.crdt_last_diff_ms.argtypes = [vp, P(C.c_double)]
@@ -370,6 +375,7 @@ EXPORTED_SYMBOLS = [
     "crdt_last_materialize_ms", "crdt_set_content_copies", "crdt_canon_counts", "crdt_fit", "crdt_mem_bytes", "crdt_apply_local_probed", "crdt_set_share_streams", "crdt_set_device_intern", "crdt_set_query_kernel", "crdt_device_bytes",
     "crdt_fit_note", "crdt_reseed_random_async", "crdt_digest_dev_async", "crdt_test_fail_alloc_after",
     "crdt_doc_version", "crdt_diff_async", "crdt_diff_between_async", "crdt_diff_counts", "crdt_diff_read", "crdt_last_diff_ms",
+    "crdt_version_vector", "crdt_version_vector_dev_async", "crdt_diff_vv_async", "crdt_diff_vv_closed", "crdt_test_set_vv_lds_words",
     "crdt_checkout_async", "crdt_checkout_lens", "crdt_checkout_read", "crdt_checkout_digest", "crdt_pos_to_loc_at",
     "crdt_loc_to_pos_at", "crdt_pos_to_loc_at_dev_async", "crdt_loc_to_pos_at_dev_async", "crdt_last_checkout_ms",
     "crdt_blame_async", "crdt_blame_counts", "crdt_blame_read", "crdt_last_blame_ms",
@@ -848,6 +854,78 @@ class Engine:
         if strict and bad.size:
             raise CrdtError(f"diff_between failed rc=-100 for indexes {bad.tolist()}: a version above the document's, or a poisoned document")
         return [None if int(counts[0][i]) == 0xFFFFFFFF else self.diff_read(i, counts) for i in range(len(counts[0]))]
+
+    # --- causal versions: version vectors (crdt_gpu.h "Causal versions")
+    EXPORT_SIZES_AGENTS = 9  # crdt_export_sizes: the index of a document's agent count
+
+    def _n_agents(self, docs) -> np.ndarray:
+        """agent count of every listed document: the length of its version vectors (one
+        crdt_export_sizes call per distinct document; pass n_agents to version_vector to skip it)"""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        s = np.zeros(12, np.uint64)
+        seen = {}
+        for x in d.tolist():
+            if x not in seen:
+                _check(self.L.crdt_export_sizes(self.h, x, _p(s, C.c_uint64)), "export_sizes")
+                seen[x] = int(s[self.EXPORT_SIZES_AGENTS])
+        return np.array([seen[x] for x in d.tolist()], np.uint32)
+
+    def version_vector(self, docs, versions=None, n_agents=None):
+        """[vv (n_agents,) u32] per docs[q]: the version vector of the order prefix versions[q] of
+        docs[q] (None: now), vv[a] = the seqs of agent id a among the orders below it.  n_agents:
+        the documents' agent counts if the caller holds them (one number, or one per query; a
+        count below a document's raises CrdtError); else they are asked for, document by document"""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        v = None if versions is None else np.ascontiguousarray(versions, dtype=np.uint32)
+        if d.ndim != 1 or (v is not None and v.shape != d.shape):
+            raise ValueError("version_vector: docs and versions are 1-d and of equal length")
+        na = self._n_agents(d) if n_agents is None else np.broadcast_to(np.asarray(n_agents, np.uint32), d.shape)
+        off = np.zeros(d.shape[0] + 1, np.uint64)
+        off[1:] = np.cumsum(na, dtype=np.uint64)
+        out = np.zeros(int(off[-1]), np.uint32)
+        _check(self.L.crdt_version_vector(self.h, d.shape[0], _p(d), None if v is None else _p(v), _p(off, C.c_uint64), _p(out)),
+               "version_vector")
+        return [out[int(off[q]):int(off[q + 1])].copy() for q in range(d.shape[0])]
+
+    def diff_vv_async(self, docs, from_vv, to_vv):
+        """compute the patches from the causal version from_vv[i] to the causal version to_vv[i] of
+        docs[i] (no duplicates; two version vectors per index, sequences of per-agent seq counts,
+        the shorter of a pair padded with 0) on the device; the result replaces the last diff
+        result and is read like one (diff_counts, diff_read, diff_ms, rebase_async("diff"))"""
+        d = np.ascontiguousarray(docs, dtype=np.uint32)
+        if d.ndim != 1 or len(from_vv) != d.shape[0] or len(to_vv) != d.shape[0]:
+            raise ValueError("diff_vv: docs is 1-d, with a from and a to vector per document")
+        fa = [np.asarray(x, dtype=np.uint32).ravel() for x in from_vv]
+        ta = [np.asarray(x, dtype=np.uint32).ravel() for x in to_vv]
+        ln = np.array([max(len(x), len(y)) for x, y in zip(fa, ta)], dtype=np.uint64)
+        off = np.zeros(d.shape[0] + 1, np.uint64)
+        off[1:] = np.cumsum(ln, dtype=np.uint64)
+        f, t = np.zeros(int(off[-1]) + 1, np.uint32), np.zeros(int(off[-1]) + 1, np.uint32)
+        for i, (x, y) in enumerate(zip(fa, ta)):
+            f[int(off[i]):int(off[i]) + len(x)] = x
+            t[int(off[i]):int(off[i]) + len(y)] = y
+        _check(self.L.crdt_diff_vv_async(self.h, d.shape[0], _p(d), _p(off, C.c_uint64), _p(f), _p(t)), "diff_vv_async")
+        self._diff_n = d.shape[0]
+
+    def diff_vv(self, docs, from_vv, to_vv, strict: bool = True):
+        """what diff_between() returns, for the patches that turn the text of docs[i] at the causal
+        version from_vv[i] into its text at to_vv[i].  An index without a result (a vector longer
+        than the document's agents, an entry above the agent's next seq, a poisoned document)
+        raises CrdtError, or is None with strict=False; the other indexes are not affected."""
+        self.diff_vv_async(docs, from_vv, to_vv)
+        counts = self.diff_counts()
+        bad = np.flatnonzero(counts[0] == 0xFFFFFFFF)
+        if strict and bad.size:
+            raise CrdtError(f"diff_vv failed rc=-100 for indexes {bad.tolist()}: a vector out of bounds, or a poisoned document")
+        return [None if int(counts[0][i]) == 0xFFFFFFFF else self.diff_read(i, counts) for i in range(len(counts[0]))]
+
+    def diff_vv_closed(self):
+        """(closed_from, closed_to) bool arrays per index of the last diff_vv: the side's set of
+        orders is causally closed (every txn it touches with its parents, and from its first order)"""
+        n = getattr(self, "_diff_n", 0)
+        a, b = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        _check(self.L.crdt_diff_vv_closed(self.h, _p(a, C.c_uint8), _p(b, C.c_uint8)), "diff_vv_closed")
+        return a.astype(bool), b.astype(bool)
 
     def diff_ms(self) -> float:
         """device time of the last diff (HIP events)"""

@@ -21,6 +21,7 @@
 #include "edits.h"
 #include "edits2.h"
 #include "rebase.h"
+#include "diff_vv.h"
 
 using namespace crdt;
 
@@ -42,6 +43,7 @@ thread_local std::string g_last_error;
 std::mutex g_mem_mu;
 std::unordered_map<void*, u64> g_mem_size;
 u64 g_mem_cur = 0, g_mem_peak = 0;
+u32 g_vv_lds_words = DIFF_MARK_WORDS;  // crdt_test_set_vv_lds_words: the LDS budget of k_vv_mark launches
 long long g_fail_alloc_after = -1;  // crdt_test_fail_alloc_after: the allocations left before one fails
 thread_local bool g_alloc_oom = false;  // a dalloc of this thread ran out of memory since the flag was cleared
 template <class T>
@@ -430,6 +432,13 @@ struct crdt_engine {
   DevBuf<u32> diff_to, diff_bm_to;  // crdt_diff_between_async: the versions to diff to and their bitmaps
   DevBuf<u64> diff_bm_base;
   DevBuf<Patch> diff_pat;
+  // crdt_diff_vv_async: the two sides' vectors and their offsets, k_vv_mark's per-index flags;
+  // diff_is_vv: the diff result is that call's (crdt_diff_vv_closed)
+  std::vector<u32> vv_from_h, vv_to_h, vv_flag_h;
+  std::vector<u64> vv_off_h;
+  DevBuf<u32> vv_from, vv_to, vv_flag_a, vv_flag_b;
+  DevBuf<u64> vv_off;
+  bool diff_is_vv = false;
   // checkout (crdt_checkout_async).  The arrays are copies and stay readable; the _at queries also
   // read the published index, so they need pub_epoch (counts publishes) unchanged and the index
   // still current.
@@ -552,6 +561,7 @@ struct crdt_engine {
     qbuf_bytes = 0;
     each_job([](auto& j) { j.free(); });
     free_bufs(diff_docs, diff_since, diff_bm_base, diff_bm, diff_pat, diff_io, diff_it, diff_to, diff_bm_to);
+    free_bufs(vv_from, vv_to, vv_flag_a, vv_flag_b, vv_off);
     free_bufs(co_docs, co_ver, co_bm_base, co_sp_base, co_bm, co_rk, co_opos, co_ord, co_text);
     free_bufs(blame_docs, blame_runs, enc_docs, enc_sp_base, enc_samples, enc_units, ln_tab, fd_pat, fd_tab);
     free_bufs(ed_docs, ed_since, ed_bm_base, ed_bm, ed_words, ed_edits, ed_units, ed_to, ed_bm_to, ed_planes, rb_ch, rb_un);
@@ -1524,6 +1534,7 @@ struct crdt_engine {
     int r = set_device();
     if (r) return r;
     diff.drop();
+    diff_is_vv = false;
     if (!published) {
       r = publish();
       if (r) return r;
@@ -1575,6 +1586,7 @@ struct crdt_engine {
     int r = set_device();
     if (r) return r;
     diff.drop();
+    diff_is_vv = false;
     if (!published) {
       r = publish();
       if (r) return r;
@@ -1631,6 +1643,84 @@ struct crdt_engine {
     return diff.stop();
   }
   Diff2IO diff2_view() const { return Diff2IO{diff_view(), diff_to.p, diff_bm_to.p}; }
+  // crdt_diff_vv_async: run_diff_between with a set of orders on either side, each given as a
+  // version vector (csrc/diff_vv.h).  k_vv_mark runs twice on the diff's bitmap buffers, which
+  // hold a pair of bitmaps per index here (member, deleted by the set), and k_diff2_sets counts and
+  // writes into the diff's own result.
+  int run_diff_vv(u64 n, const uint32_t* dl, const uint64_t* off, const uint32_t* from, const uint32_t* to) {
+    int r = set_device();
+    if (r) return r;
+    diff.drop();
+    diff_is_vv = false;
+    if (!published) {
+      r = publish();
+      if (r) return r;
+    }
+    r = diff.begin(n);
+    if (r) return r;
+    if (!n) {
+      diff.valid = diff_is_vv = true;
+      return 0;
+    }
+    u64 nvv = off[n] - off[0];
+    diff_docs_h.assign(dl, dl + n);
+    vv_off_h.resize(n + 1);
+    for (u64 i = 0; i <= n; i++) vv_off_h[i] = off[i] - off[0];
+    vv_from_h.clear();
+    vv_to_h.clear();
+    if (nvv) {
+      vv_from_h.assign(from + off[0], from + off[n]);
+      vv_to_h.assign(to + off[0], to + off[n]);
+    }
+    diff_bm_h.resize(n);
+    const u32 budget = std::min<u32>(g_vv_lds_words, DIFF_MARK_WORDS);
+    u64 words = 0;
+    u32 xw = 0;           // the largest listed bitmap pair that k_vv_mark builds in LDS
+    bool all_lds = true;  // ... and every listed one is (no bitmap word needs zeroing)
+    for (u64 i = 0; i < n; i++) {
+      diff_bm_h[i] = words;
+      u32 pw = 2u * pub_words(seg_h[dl[i]].ord_cap);
+      words += pw;
+      if (pw <= budget) xw = std::max(xw, pw);
+      else all_lds = false;
+    }
+    r = grow_bufs(n, diff_docs, diff_bm_base, vv_flag_a, vv_flag_b);
+    if (!r) r = vv_off.grow(stream, n + 1);
+    if (!r) r = grow_bufs(nvv, vv_from, vv_to);
+    if (!r) r = grow_bufs(words, diff_bm, diff_bm_to);
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(diff_docs.p, diff_docs_h.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(diff_bm_base.p, diff_bm_h.data(), n * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(vv_off.p, vv_off_h.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream));
+    if (nvv) {
+      HIPCHK(hipMemcpyAsync(vv_from.p, vv_from_h.data(), nvv * 4, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(vv_to.p, vv_to_h.data(), nvv * 4, hipMemcpyHostToDevice, stream));
+    }
+    r = diff.start();
+    if (r) return r;
+    if (!all_lds) {
+      HIPCHK(hipMemsetAsync(diff_bm.p, 0, words * 4, stream));
+      HIPCHK(hipMemsetAsync(diff_bm_to.p, 0, words * 4, stream));
+    }
+    Pools pv = pools_view(pools);
+    PubOut ov = pub_view();
+    VvIO ma{diff_docs.p, vv_off.p, vv_from.p, diff_bm_base.p, diff_bm.p, vv_flag_a.p};
+    VvIO mb{diff_docs.p, vv_off.p, vv_to.p, diff_bm_base.p, diff_bm_to.p, vv_flag_b.p};
+    const size_t lds = (size_t)xw * 4;
+    hipLaunchKernelGGL(k_vv_mark, dim3((u32)n), dim3(DIFF_T), lds, stream, pv, ma, (u32)n, xw);
+    hipLaunchKernelGGL(k_vv_mark, dim3((u32)n), dim3(DIFF_T), lds, stream, pv, mb, (u32)n, xw);
+    hipLaunchKernelGGL(k_diff2_sets<false>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, diff_vv_view(), (u32)n);
+    hipLaunchKernelGGL(k_result_scan<DiffRes>, dim3(1), dim3(DIFF_SCAN_T), 0, stream, diff.res.p, (u32)n, diff.tot.p);
+    r = diff.read_totals();
+    if (!r) r = diff_pat.grow(stream, diff.tot_h[0]);
+    if (!r) r = grow_bufs(diff.tot_h[1], diff_io, diff_it);
+    if (r) return r;
+    hipLaunchKernelGGL(k_diff2_sets<true>, dim3((u32)n), dim3(DIFF_T), 0, stream, pv, ov, diff_vv_view(), (u32)n);  // (the grown arrays)
+    r = diff.stop();
+    diff_is_vv = r == 0;
+    return r;
+  }
+  DiffVvIO diff_vv_view() const { return DiffVvIO{diff2_view(), vv_flag_a.p, vv_flag_b.p}; }
 
   EdIO ed_view() const {
     EdIO io{};
@@ -2270,6 +2360,7 @@ int crdt_engine_create(const crdt_cfg* cfg, crdt_engine** out) {
   (void)hipFuncSetAttribute((const void*)k_pub_index, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)pubx_lds_bytes(PUBX_MAX_WORDS));
   (void)hipFuncSetAttribute((const void*)k_diff_mark, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIFF_MARK_WORDS * 4u));
+  (void)hipFuncSetAttribute((const void*)k_vv_mark, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(DIFF_MARK_WORDS * 4u));
   *out = e;
   return 0;
 }
@@ -2296,6 +2387,12 @@ uint64_t crdt_num_docs(const crdt_engine* e) { return e ? e->n_docs : 0; }
 int crdt_test_fail_alloc_after(long long k) {
   std::lock_guard<std::mutex> g(g_mem_mu);
   g_fail_alloc_after = k < 0 ? -1 : k;
+  return 0;
+}
+
+int crdt_test_set_vv_lds_words(uint32_t words) {
+  std::lock_guard<std::mutex> g(g_mem_mu);
+  g_vv_lds_words = std::min<u32>(words, DIFF_MARK_WORDS);
   return 0;
 }
 
@@ -3071,6 +3168,7 @@ uint64_t crdt_mem_bytes(const crdt_engine* e) {
   return e->pools.bytes + e->rec_cap * sizeof(Rec) + e->content_cap * 4 + e->text_cap * 4 + e->canon_alloc * 28 +
          e->pub_alloc * 4 + e->probe_cap * 16 +
          buf_bytes(e->diff.res, e->diff_docs, e->diff_since, e->diff_bm_base, e->diff_bm, e->diff_pat, e->diff_io, e->diff_it, e->diff_to, e->diff_bm_to) +
+         buf_bytes(e->vv_from, e->vv_to, e->vv_flag_a, e->vv_flag_b, e->vv_off) +
          buf_bytes(e->co.res, e->co_docs, e->co_ver, e->co_bm_base, e->co_sp_base, e->co_bm, e->co_rk, e->co_opos, e->co_ord, e->co_text) +
          buf_bytes(e->blame.res, e->blame_docs, e->blame_runs, e->enc.res, e->enc_docs, e->enc_sp_base, e->enc_samples, e->enc_units) +
          buf_bytes(e->ln.res, e->ln_tab, e->fd.res, e->fd_tab, e->fd_pat) +
@@ -3162,6 +3260,87 @@ int crdt_diff_between_async(crdt_engine* e, uint64_t n_docs, const uint32_t* doc
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e) || (n_docs && (!docs || !from || !to)) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
   return oom_as_nomem([&] { return e->run_diff_between(n_docs, docs, from, to); });
+}
+
+int crdt_version_vector_dev_async(crdt_engine* e, uint64_t n, const uint32_t* doc, const uint32_t* version, const uint64_t* vv_off,
+                                  uint32_t* vv_out) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || n > 0x7FFFFFFFull || (n && (!doc || !vv_off || !vv_out))) return CRDT_E_ARG;
+  int r = e->set_device();
+  if (r) return r;
+  if (!n) return 0;
+  hipLaunchKernelGGL(k_vv_of, dim3((u32)n), dim3(VV_OF_T), 0, e->stream, e->pools_view(e->pools), (u32)e->n_docs, (u32)n, doc, version,
+                     vv_off, vv_out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int crdt_version_vector(crdt_engine* e, uint64_t n, const uint32_t* doc, const uint32_t* version, const uint64_t* vv_off, uint32_t* vv_out) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || n > 0x7FFFFFFFull || (n && (!doc || !vv_off || !vv_out))) return CRDT_E_ARG;
+  if (!n) return 0;
+  int r = e->pull_states();
+  if (r) return r;
+  for (uint64_t q = 0; q < n; q++) {
+    if (doc[q] >= e->n_docs || vv_off[q + 1] < vv_off[q] || vv_off[q] < vv_off[0]) return CRDT_E_ARG;
+    const DocState& st = e->st_h[doc[q]];
+    if (st.status != ST_OK && st.status != ST_NEED_CAPACITY) {
+      g_last_error = "version_vector: a poisoned document";
+      return CRDT_E_ARG;
+    }
+    if (vv_off[q + 1] - vv_off[q] < st.n_agents || (version && version[q] > st.next_order)) {
+      g_last_error = "version_vector: a slot smaller than the document's agents, or a version above the document's";
+      return CRDT_E_ARG;
+    }
+  }
+  // staged in the query scratch: doc, version, the offsets (from vv_off[0]) and the vectors
+  const u64 nvv = vv_off[n] - vv_off[0];
+  const u64 o_off = 0, o_doc = (n + 1) * 8, o_ver = o_doc + n * 4, o_out = o_ver + n * 4;
+  r = e->scratch(o_out + nvv * 4 + 64);
+  if (r) return r;
+  char* base = (char*)e->qbuf;
+  std::vector<u64> off(n + 1);
+  for (uint64_t q = 0; q <= n; q++) off[q] = vv_off[q] - vv_off[0];
+  HIPCHK(hipMemcpyAsync(base + o_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(base + o_doc, doc, n * 4, hipMemcpyHostToDevice, e->stream));
+  if (version) HIPCHK(hipMemcpyAsync(base + o_ver, version, n * 4, hipMemcpyHostToDevice, e->stream));
+  r = crdt_version_vector_dev_async(e, n, (const u32*)(base + o_doc), version ? (const u32*)(base + o_ver) : nullptr,
+                                    (const u64*)(base + o_off), (u32*)(base + o_out));
+  if (r) return r;
+  if (nvv) HIPCHK(hipMemcpyAsync(vv_out + vv_off[0], base + o_out, nvv * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));  // (off lives until here)
+  return 0;
+}
+
+int crdt_diff_vv_async(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint64_t* vv_off, const uint32_t* from_vv,
+                       const uint32_t* to_vv) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e) || (n_docs && (!docs || !vv_off)) || !ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
+  for (uint64_t i = 0; i < n_docs; i++)
+    if (vv_off[i + 1] < vv_off[i]) return CRDT_E_ARG;
+  if (n_docs && vv_off[n_docs] > vv_off[0] && (!from_vv || !to_vv)) return CRDT_E_ARG;
+  return oom_as_nomem([&] { return e->run_diff_vv(n_docs, docs, vv_off, from_vv, to_vv); });
+}
+
+int crdt_diff_vv_closed(crdt_engine* e, uint8_t* closed_from, uint8_t* closed_to) {
+  if (poisoned(e)) return CRDT_E_NOMEM;
+  if (!valid(e)) return CRDT_E_ARG;
+  if (!e->diff.valid || !e->diff_is_vv) {
+    g_last_error = "diff_vv_closed: the last diff result was not made by crdt_diff_vv_async";
+    return CRDT_E_ARG;
+  }
+  int r = e->diff.finish();
+  if (r) return r;
+  u64 n = e->diff.n;
+  if (!n) return 0;
+  e->vv_flag_h.resize(2 * n);
+  HIPCHK(hipMemcpy(e->vv_flag_h.data(), e->vv_flag_a.p, n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(e->vv_flag_h.data() + n, e->vv_flag_b.p, n * 4, hipMemcpyDeviceToHost));
+  for (u64 i = 0; i < n; i++) {
+    if (closed_from) closed_from[i] = (e->vv_flag_h[i] & (VV_BAD | VV_CLOSED)) == VV_CLOSED;
+    if (closed_to) closed_to[i] = (e->vv_flag_h[n + i] & (VV_BAD | VV_CLOSED)) == VV_CLOSED;
+  }
+  return 0;
 }
 
 int crdt_diff_counts(crdt_engine* e, uint32_t* n_patches, uint32_t* n_ins) {

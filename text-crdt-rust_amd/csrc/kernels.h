@@ -1481,9 +1481,20 @@ __device__ __forceinline__ u32 below_mask(u32 w, u32 v) {
 struct D2Word {
   u32 o, n, K, C, X;
 };
-__device__ __forceinline__ D2Word d2_word(const u32* bma, const u32* bmb, u32 w, u32 a, u32 b, u32 from, u32 to) {
+// (SETS, csrc/diff_vv.h: either side is a set of orders given as a member bitmap, ma / mb, in
+// place of "the orders below from / to")
+template <bool SETS = false>
+__device__ __forceinline__ D2Word d2_word(const u32* bma, const u32* bmb, u32 w, u32 a, u32 b, u32 from, u32 to,
+                                          const u32* ma = nullptr, const u32* mb = nullptr) {
   u32 m = range_mask(w, a, b);
-  u32 o = m & below_mask(w, from) & ~bma[w], n = m & below_mask(w, to) & ~bmb[w];
+  u32 o, n;
+  if (SETS) {
+    o = m & ma[w] & ~bma[w];
+    n = m & mb[w] & ~bmb[w];
+  } else {
+    o = m & below_mask(w, from) & ~bma[w];
+    n = m & below_mask(w, to) & ~bmb[w];
+  }
   return D2Word{o, n, o & n, o ^ n, o | n};
 }
 // the patch starts of a word: C items whose last X predecessor in the word is a K, and the word's
@@ -1531,17 +1542,17 @@ __device__ __forceinline__ void d2_emit(u32 S, const D2Word& x, u32 p, u32 n0, u
 // span; its patches are written by the lanes that hold their words, and its inserted items with
 // contiguous stores: lane l takes item t + l of the step's, finds its word by the 6-step search
 // over the scan (as k_diff) and its bit by a 5-step search over the word.
-template <bool WRITE>
+template <bool WRITE, bool SETS = false>
 __device__ __forceinline__ D2Sum d2_long(const u32* bma, const u32* bmb, u32 ua, u32 ub, u32 from, u32 to, u32 l, bool open,
                                          u32 p, u32 n0, u32 d0, u32 i0, Patch* pat, u32 my_pat, u32* io, u32* it, u32 my_ins,
-                                         bool text, const u32* src) {
+                                         bool text, const u32* src, const u32* ma = nullptr, const u32* mb = nullptr) {
   D2Sum t{0u, 0u, 0u, 0u, 0u, 0u, 0u};
   u32 wl = (ub - 1u) >> 5;
   u64 lower = (1ull << l) - 1ull;
   for (u32 w0 = ua >> 5; w0 <= wl; w0 += 64u) {
     u32 w = w0 + l;
     D2Word x{0u, 0u, 0u, 0u, 0u};
-    if (w <= wl) x = d2_word(bma, bmb, w, ua, ub, from, to);
+    if (w <= wl) x = d2_word<SETS>(bma, bmb, w, ua, ub, from, to, ma, mb);
     bool h = x.X != 0u;
     bool lastc = h && d2_last_c(x);
     u64 mO = ballot(lastc), mC = ballot(h && !lastc);
@@ -1597,18 +1608,26 @@ __device__ __forceinline__ D2Sum d2_long(const u32* bma, const u32* bmb, u32 ua,
 // more, with the true state before it, and the lane writes those patches; the wave writes its
 // short spans' inserted items together and a long span's in d2_long, with contiguous stores; the
 // last sweep over the document's patches turns neighbouring starts into del_len and ins_len.
-template <bool WRITE>
-__global__ __launch_bounds__(DIFF_T) void k_diff2(Pools P, PubOut O, Diff2IO E, u32 n) {
+// (The walk itself is d2_walk, which k_diff2 instantiates for two versions and k_diff2_sets,
+// csrc/diff_vv.h, for two sets of orders: SETS reads each side's member bitmap at the index's
+// bm_base and its "deleted by the set" bitmap in the pub_words(ord_cap) words after it, and takes
+// the sides' k_vv_mark flags fa / fb in place of the two version checks.)
+constexpr u32 VV_BAD = 1u;     // k_vv_mark: a vector out of bounds, or a poisoned document
+constexpr u32 VV_CLOSED = 2u;  // k_vv_mark: the set is causally closed
+template <bool WRITE, bool SETS>
+__device__ __forceinline__ void d2_walk(const Pools& P, const PubOut& O, const Diff2IO& E, u32 n, const u32* fa, const u32* fb) {
   u32 i = blockIdx.x;
   if (i >= n) return;
   const DiffIO& D = E.d;
   u32 d = D.docs[i];
   u32 tid = threadIdx.x, l = lane_id(), wv = uni(tid >> 6);
   i32 stt = P.st[d].status;
-  u32 no = P.st[d].next_order, from = D.since[i], to = E.to[i];
+  u32 no = P.st[d].next_order, from = SETS ? no : D.since[i], to = SETS ? no : E.to[i];
   u64 cb = D.cbase[d], cl = D.clen[d];
   bool text = cb != NO_CONTENT && cl >= (u64)no;
-  if ((stt != ST_OK && stt != ST_NEED_CAPACITY) || from > no || to > no) {
+  bool bad = (stt != ST_OK && stt != ST_NEED_CAPACITY) || from > no || to > no;
+  if (SETS) bad = bad || ((fa[i] | fb[i]) & VV_BAD) != 0u;
+  if (bad) {
     if (!WRITE && tid == 0) D.res[i] = DiffRes{0u, 0u, DIFF_BAD, no, 0ull, 0ull};
     return;
   }
@@ -1619,6 +1638,13 @@ __global__ __launch_bounds__(DIFF_T) void k_diff2(Pools P, PubOut O, Diff2IO E, 
   u32 top = min(max(from, to), sg.ord_cap);
   const u32* bma = D.bm + D.bm_base[i];
   const u32* bmb = E.bm_b + D.bm_base[i];
+  const u32* ma = nullptr;
+  const u32* mb = nullptr;
+  if (SETS) {
+    u32 nw = pub_words(sg.ord_cap);
+    ma = bma; mb = bmb;
+    bma += nw; bmb += nw;
+  }
   u32 my_pat = 0, my_ins = 0;  // (WRITE) this index's counts from the first sweep: every store stays below them
   Patch* pat = nullptr;
   u32* io = nullptr;
@@ -1644,7 +1670,7 @@ __global__ __launch_bounds__(DIFF_T) void k_diff2(Pools P, PubOut O, Diff2IO E, 
     if (shrt) {
       bool open = true;
       for (u32 w = a >> 5; w <= ((b - 1u) >> 5); w++) {
-        D2Word x = d2_word(bma, bmb, w, a, b, from, to);
+        D2Word x = d2_word<SETS>(bma, bmb, w, a, b, from, to, ma, mb);
         if (x.X) {
           if (!m.has) {
             m.has = 1u;
@@ -1668,8 +1694,8 @@ __global__ __launch_bounds__(DIFF_T) void k_diff2(Pools P, PubOut O, Diff2IO E, 
     for (u64 bg = big; bg;) {
       u32 s = (u32)__builtin_ctzll(bg);
       bg &= bg - 1ull;
-      D2Sum t = d2_long<false>(bma, bmb, rdlane(a, s), rdlane(b, s), from, to, l, true, 0u, 0u, 0u, 0u, nullptr, 0u, nullptr,
-                               nullptr, 0u, false, nullptr);
+      D2Sum t = d2_long<false, SETS>(bma, bmb, rdlane(a, s), rdlane(b, s), from, to, l, true, 0u, 0u, 0u, 0u, nullptr, 0u,
+                                     nullptr, nullptr, 0u, false, nullptr, ma, mb);
       if (l == s) m = t;
     }
     // state after each span: its last X item is a C (a patch is open) or a K (none is)
@@ -1705,7 +1731,7 @@ __global__ __launch_bounds__(DIFF_T) void k_diff2(Pools P, PubOut O, Diff2IO E, 
         bool open = open_before;
         u32 pp = p, n0 = Nex, d0 = Dex, i0 = Iex;
         for (u32 w = a >> 5; w <= ((b - 1u) >> 5); w++) {
-          D2Word x = d2_word(bma, bmb, w, a, b, from, to);
+          D2Word x = d2_word<SETS>(bma, bmb, w, a, b, from, to, ma, mb);
           u32 S = d2_starts(x, open);
           d2_emit(S, x, pp, n0, d0, i0, pat, my_pat);
           pp += (u32)__popc(S);
@@ -1737,7 +1763,7 @@ __global__ __launch_bounds__(DIFF_T) void k_diff2(Pools P, PubOut O, Diff2IO E, 
           u32 sa = shfl(a, s), sb = shfl(b, s);
           if (walk) {
             for (u32 w = sa >> 5; w <= ((sb - 1u) >> 5); w++) {
-              D2Word x = d2_word(bma, bmb, w, sa, sb, from, to);
+              D2Word x = d2_word<SETS>(bma, bmb, w, sa, sb, from, to, ma, mb);
               u32 im = x.n & ~x.o;
               u32 c = (u32)__popc(im);
               if (r < c) {
@@ -1756,8 +1782,9 @@ __global__ __launch_bounds__(DIFF_T) void k_diff2(Pools P, PubOut O, Diff2IO E, 
       for (u64 bg = big; bg;) {
         u32 s = (u32)__builtin_ctzll(bg);
         bg &= bg - 1ull;
-        d2_long<true>(bma, bmb, rdlane(a, s), rdlane(b, s), from, to, l, rdlane(open_before ? 1u : 0u, s) != 0u, rdlane(p, s),
-                      rdlane(Nex, s), rdlane(Dex, s), rdlane(Iex, s), pat, my_pat, io, it, my_ins, text, src);
+        d2_long<true, SETS>(bma, bmb, rdlane(a, s), rdlane(b, s), from, to, l, rdlane(open_before ? 1u : 0u, s) != 0u,
+                            rdlane(p, s), rdlane(Nex, s), rdlane(Dex, s), rdlane(Iex, s), pat, my_pat, io, it, my_ins, text, src,
+                            ma, mb);
       }
     }
     for (u32 w = 0; w < DIFF_WAVES; w++) {
@@ -1795,6 +1822,10 @@ __global__ __launch_bounds__(DIFF_T) void k_diff2(Pools P, PubOut O, Diff2IO E, 
       pat[p].ins_len = i1 - i0;
     }
   }
+}
+template <bool WRITE>
+__global__ __launch_bounds__(DIFF_T) void k_diff2(Pools P, PubOut O, Diff2IO E, u32 n) {
+  d2_walk<WRITE, false>(P, O, E, n, nullptr, nullptr);
 }
 
 template <class T>
