@@ -17,8 +17,13 @@
  *     skipped.  This mirrors "the reference panics": the document is dead, the rest live on.
  *   - Return value of every function: 0 = ok, < 0 = API error (CRDT_E_*).
  *   - A stage / apply call names each document at most once (its docs[] has no duplicates);
- *     a call that names a document twice returns CRDT_E_ARG and changes nothing.  Every stage
+ *     a call that names a document twice returns CRDT_E_ARG and changes nothing.  Likewise a
+ *     remote call with a malformed wire batch: every wire of the call is parsed before any
+ *     author is interned, so a call that returns CRDT_E_WIRE changes nothing either (agent ids
+ *     handed out later are those of a history in which the call never happened).  Every stage
  *     call replaces the staged streams of all documents (documents not named get none).
+ *   - No exception crosses this boundary: host memory that runs out while a stage / apply call
+ *     parses and encodes its input is CRDT_E_NOMEM.
  */
 #ifndef CRDT_GPU_H
 #define CRDT_GPU_H
@@ -101,7 +106,17 @@ int crdt_apply_local(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, cons
  *                         n_parents x {name, seq},
  *                         n_ops x {kind (0 Ins, 1 Del), a_name, a_seq, b_name, b_seq, len} }
  *   Ins: a = origin_left, b = origin_right, len = chars inserted.  Del: a = target, len.
- *   The name "ROOT" denotes the root id (doc.rs:68). */
+ *   The name "ROOT" denotes the root id (doc.rs:68).
+ *
+ * A wire is a peer's input and is checked as such.  CRDT_E_WIRE: wrong magic, a count or a name
+ * length that the remaining bytes cannot hold (counts are checked before anything is sized by
+ * them), a name index outside the name table, a kind other than 0 or 1, a batch that ends early.
+ * Names are compared as bytes, pad bytes and a Del's b are not looked at, and bytes after the last
+ * txn are ignored.  CRDT_E_ARG: a wire pointer that is NULL or not 4-byte aligned (the batch is
+ * read in place as u32s; the pointer is not dereferenced).
+ * Limits: a txn holds at most 65,535 parents and 2^26 - 1 ops, an op at most 2^28 - 1 items.  A
+ * txn beyond them is well-formed wire but cannot be replayed: its document stops at that txn with
+ * CRDT_ERR_BAD_INPUT, unchanged by it, like one with a zero-length op. */
 int crdt_apply_remote_wire(crdt_engine* e, uint64_t n_docs, const uint32_t* docs,
                            const uint8_t* const* wire, const uint64_t* wire_len, int32_t* doc_status);
 

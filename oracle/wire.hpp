@@ -56,21 +56,26 @@ inline bool parse(const uint8_t* p, size_t len, Batch& b) {
   };
   u32 magic, nn;
   if (!rd(magic) || magic != MAGIC || !rd(nn)) return false;
+  // every count is checked against the bytes that remain before anything is sized by it (a name
+  // takes at least 4 bytes, a txn 16, a parent 8, an op 24)
+  if (4ull * nn > len - off) return false;
   b.names.resize(nn);
   for (u32 i = 0; i < nn; i++) {
     u32 bl;
-    if (!rd(bl) || off + bl > len) return false;
+    if (!rd(bl) || bl > len - off) return false;
     b.names[i].assign((const char*)p + off, bl);
-    off += (bl + 3) & ~3u;
+    off += ((size_t)bl + 3) & ~(size_t)3;
   }
   u32 nt;
   if (!rd(nt)) return false;
+  if (16ull * nt > len - off) return false;
   b.txns.resize(nt);
   for (u32 t = 0; t < nt; t++) {
     Txn& x = b.txns[t];
     u32 np, no;
     if (!rd(x.id.name) || !rd(x.id.seq) || !rd(np) || !rd(no)) return false;
     if (x.id.name >= nn) return false;
+    if (8ull * np + 24ull * no > len - off) return false;
     x.parents.resize(np);
     for (u32 i = 0; i < np; i++) {
       if (!rd(x.parents[i].name) || !rd(x.parents[i].seq) || x.parents[i].name >= nn) return false;

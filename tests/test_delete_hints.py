@@ -93,7 +93,7 @@ def ref_encode(txns, table):
             if ok:
                 recs.append(((REC_RC << 28) | ((1 if k else 0) << 27) | (ln << 16) | author, seq, e2, e3))
                 continue
-        if len(ops) > 0x03FFFFFF:
+        if len(ops) > 0x03FFFFFF or len(parents) > 0xFFFF:  # a count past its header field: malformed
             zero = True
         recs.append(((REC_RTXN << 28) | (int(zero) << 27) | (int(has_del) << 26) | (len(ops) & 0x03FFFFFF),
                      (author & 0xFFFF) | ((len(parents) & 0xFFFF) << 16), seq, min(tl, M32)))

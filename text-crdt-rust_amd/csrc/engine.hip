@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <exception>
 #include <map>
 #include <mutex>
 #include <string>
@@ -948,7 +949,17 @@ struct crdt_engine {
   }
 
   // Stage per-document record streams (host-encoded) and grow capacities if needed.
+  // (a host allocation that fails in here may leave the tables half-changed: the engine is
+  // poisoned, like after a relayout that failed part-way)
   int stage(const std::vector<u64>& doc_ids, std::vector<const std::vector<Rec>*>& streams, std::vector<StreamNeeds>& needs) {
+    try {
+      return stage_body(doc_ids, streams, needs);
+    } catch (const std::exception&) {
+      poisoned = true;
+      return CRDT_E_NOMEM;
+    }
+  }
+  int stage_body(const std::vector<u64>& doc_ids, std::vector<const std::vector<Rec>*>& streams, std::vector<StreamNeeds>& needs) {
     int r = set_device();
     if (r) return r;
     HIPCHK(hipStreamSynchronize(stream));
@@ -2253,6 +2264,20 @@ static int oom_as_nomem(F call) {
   return r;
 }
 
+// The staging entry points size host tables by what the caller passes in.  No exception leaves the
+// C ABI: a host allocation that fails while a call parses and encodes its input is CRDT_E_NOMEM
+// (std::bad_alloc, std::length_error: the standard containers' only throws here).  The engine's
+// device state is then as it was; crdt_engine::stage answers for what happens from there on.
+template <class F>
+static int stage_guard(F call) {
+  try {
+    return call();
+  } catch (const std::exception&) {
+    try { g_last_error = "out of host memory while staging"; } catch (...) {}
+    return CRDT_E_NOMEM;
+  }
+}
+
 // crdt_last_*_ms: the device time of a job's last call (waits for it)
 template <class J>
 static int job_ms(crdt_engine* e, J crdt_engine::*job, double* ms) {
@@ -2399,18 +2424,20 @@ int crdt_test_set_vv_lds_words(uint32_t words) {
 int crdt_agent_intern(crdt_engine* e, uint64_t n, const uint32_t* doc, const char* const* names, uint16_t* out) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e) || (n && (!doc || !names || !out))) return CRDT_E_ARG;
-  for (uint64_t i = 0; i < n; i++) {
-    if (doc[i] >= e->n_docs) return CRDT_E_ARG;
-    out[i] = (uint16_t)e->docs[doc[i]].agents.get_or_create(names[i]);
-  }
-  return 0;
+  return stage_guard([&]() -> int {
+    for (uint64_t i = 0; i < n; i++) {
+      if (doc[i] >= e->n_docs) return CRDT_E_ARG;
+      out[i] = (uint16_t)e->docs[doc[i]].agents.get_or_create(names[i]);
+    }
+    return 0;
+  });
 }
 
 // Device interning (kernels.h k_intern): the same results as crdt_agent_intern on the same call.
 // Each document named in the call forms one group: its existing names (in id order, so the
 // first-appearance numbering reproduces their ids) followed by this call's names for it.
-int crdt_agent_intern_dev(crdt_engine* e, uint64_t n, const uint32_t* doc, const uint64_t* name_off,
-                          const char* bytes, uint16_t* out, uint32_t* rank_out) {
+static int agent_intern_dev_impl(crdt_engine* e, uint64_t n, const uint32_t* doc, const uint64_t* name_off,
+                                 const char* bytes, uint16_t* out, uint32_t* rank_out) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e) || (n && (!doc || !name_off || !bytes || !out))) return CRDT_E_ARG;
   if (!n) return 0;
@@ -2520,11 +2547,15 @@ int crdt_agent_intern_dev(crdt_engine* e, uint64_t n, const uint32_t* doc, const
   }
   return 0;
 }
+int crdt_agent_intern_dev(crdt_engine* e, uint64_t n, const uint32_t* doc, const uint64_t* name_off,
+                          const char* bytes, uint16_t* out, uint32_t* rank_out) {
+  return stage_guard([&] { return agent_intern_dev_impl(e, n, doc, name_off, bytes, out, rank_out); });
+}
 
 // probes (optional): one per txn, encoded after it; probe_rec gets each probe's record index
-static int stage_local_impl(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint64_t* txn_off,
-                            const crdt_local_txn* txns, const crdt_local_op* ops,
-                            const crdt_probe* probes = nullptr, std::vector<std::vector<u32>>* probe_rec = nullptr) {
+static int stage_local_body(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint64_t* txn_off,
+                            const crdt_local_txn* txns, const crdt_local_op* ops, const crdt_probe* probes,
+                            std::vector<std::vector<u32>>* probe_rec) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e) || !docs || !txn_off || (!txns && txn_off[n_docs]) ) return CRDT_E_ARG;
   if (!ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
@@ -2550,6 +2581,11 @@ static int stage_local_impl(crdt_engine* e, uint64_t n_docs, const uint32_t* doc
     }
   }
   return e->stage(ids, sp, needs);
+}
+static int stage_local_impl(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint64_t* txn_off,
+                            const crdt_local_txn* txns, const crdt_local_op* ops,
+                            const crdt_probe* probes = nullptr, std::vector<std::vector<u32>>* probe_rec = nullptr) {
+  return stage_guard([&] { return stage_local_body(e, n_docs, docs, txn_off, txns, ops, probes, probe_rec); });
 }
 
 int crdt_apply_local_probed(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint64_t* txn_off,
@@ -2580,9 +2616,9 @@ int crdt_stage_local(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, cons
   return stage_local_impl(e, n_docs, docs, txn_off, txns, ops);
 }
 
-int crdt_stage_local_shared(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* stream_of_doc,
-                            uint32_t n_streams, const uint64_t* stream_txn_off, const crdt_local_txn* txns,
-                            const crdt_local_op* ops) {
+static int stage_local_shared_impl(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* stream_of_doc,
+                                   uint32_t n_streams, const uint64_t* stream_txn_off, const crdt_local_txn* txns,
+                                   const crdt_local_op* ops) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e) || !docs || !stream_of_doc || !stream_txn_off || !n_streams) return CRDT_E_ARG;
   if (!ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
@@ -2606,12 +2642,38 @@ int crdt_stage_local_shared(crdt_engine* e, uint64_t n_docs, const uint32_t* doc
   }
   return e->stage(ids, sp, needs);
 }
+int crdt_stage_local_shared(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint32_t* stream_of_doc,
+                            uint32_t n_streams, const uint64_t* stream_txn_off, const crdt_local_txn* txns,
+                            const crdt_local_op* ops) {
+  return stage_guard([&] { return stage_local_shared_impl(e, n_docs, docs, stream_of_doc, n_streams, stream_txn_off, txns, ops); });
+}
 
-int crdt_stage_remote_wire(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint8_t* const* wire,
-                           const uint64_t* wire_len) {
+// A wire batch is read through u32 pointers into the caller's buffer (WireView): a pointer that is
+// NULL or not 4-byte aligned is refused (CRDT_E_ARG), never dereferenced.
+static bool wire_aligned(const uint8_t* w) { return w && ((uintptr_t)w & 3u) == 0; }
+
+static int stage_remote_wire_impl(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint8_t* const* wire,
+                                  const uint64_t* wire_len) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e) || !docs || !wire || !wire_len) return CRDT_E_ARG;
   if (!ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
+  // Every wire is parsed before the first one is encoded (encoding interns its authors into the
+  // document's agent table): a call that returns CRDT_E_WIRE, like one that names a document
+  // twice, has changed nothing.  A buffer handed to several documents is parsed once.
+  std::vector<WireView> views;
+  std::vector<size_t> view_of(n_docs);
+  {
+    std::map<std::pair<const uint8_t*, uint64_t>, size_t> parsed;
+    for (uint64_t i = 0; i < n_docs; i++) {
+      if (!wire_aligned(wire[i])) return CRDT_E_ARG;
+      auto f = parsed.emplace(std::make_pair(wire[i], wire_len[i]), views.size());
+      if (f.second) {
+        views.emplace_back();
+        if (!views.back().parse(wire[i], wire_len[i])) return CRDT_E_WIRE;
+      }
+      view_of[i] = f.first->second;
+    }
+  }
   std::vector<u64> ids(n_docs);
   std::vector<std::vector<Rec>> streams(n_docs);
   std::vector<StreamNeeds> needs(n_docs);
@@ -2623,9 +2685,7 @@ int crdt_stage_remote_wire(crdt_engine* e, uint64_t n_docs, const uint32_t* docs
   for (uint64_t i = 0; i < n_docs; i++) {
     if (docs[i] >= e->n_docs) return CRDT_E_ARG;
     ids[i] = docs[i];
-    WireView wv;
-    if (!wv.parse(wire[i], wire_len[i])) return CRDT_E_WIRE;
-    encode_remote(streams[i], needs[i], e->docs[docs[i]].agents, wv);
+    encode_remote(streams[i], needs[i], e->docs[docs[i]].agents, views[view_of[i]]);
     sp[i] = &streams[i];
     auto f = first_of.emplace(std::make_pair(wire[i], wire_len[i]), i);
     if (!f.second) {
@@ -2638,11 +2698,15 @@ int crdt_stage_remote_wire(crdt_engine* e, uint64_t n_docs, const uint32_t* docs
   }
   return e->stage(ids, sp, needs);
 }
+int crdt_stage_remote_wire(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const uint8_t* const* wire,
+                           const uint64_t* wire_len) {
+  return stage_guard([&] { return stage_remote_wire_impl(e, n_docs, docs, wire, wire_len); });
+}
 
-int crdt_stage_remote_replicated(crdt_engine* e, const uint8_t* wire, uint64_t wire_len, uint32_t rename_idx,
-                                 const char* const* names) {
+static int stage_remote_replicated_impl(crdt_engine* e, const uint8_t* wire, uint64_t wire_len, uint32_t rename_idx,
+                                        const char* const* names) {
   if (poisoned(e)) return CRDT_E_NOMEM;
-  if (!valid(e) || !wire) return CRDT_E_ARG;
+  if (!valid(e) || !wire_aligned(wire)) return CRDT_E_ARG;
   WireView wv;
   if (!wv.parse(wire, wire_len)) return CRDT_E_WIRE;
   // Every document gets its own interned names; documents whose name->agent-id mapping equals
@@ -2720,9 +2784,13 @@ int crdt_stage_remote_replicated(crdt_engine* e, const uint8_t* wire, uint64_t w
   }
   return e->stage(ids, sp, needs);
 }
+int crdt_stage_remote_replicated(crdt_engine* e, const uint8_t* wire, uint64_t wire_len, uint32_t rename_idx,
+                                 const char* const* names) {
+  return stage_guard([&] { return stage_remote_replicated_impl(e, wire, wire_len, rename_idx, names); });
+}
 
-int crdt_stage_random(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const char* agent, uint32_t n_ops,
-                      uint64_t seed) {
+static int stage_random_impl(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const char* agent, uint32_t n_ops,
+                             uint64_t seed) {
   if (poisoned(e)) return CRDT_E_NOMEM;
   if (!valid(e) || !docs || !agent || n_ops == 0 || std::strcmp(agent, "ROOT") == 0) return CRDT_E_ARG;
   if (!ids_ok(e, n_docs, docs)) return CRDT_E_ARG;
@@ -2738,6 +2806,10 @@ int crdt_stage_random(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, con
     sp[i] = &streams[i];
   }
   return e->stage(ids, sp, needs);
+}
+int crdt_stage_random(crdt_engine* e, uint64_t n_docs, const uint32_t* docs, const char* agent, uint32_t n_ops,
+                      uint64_t seed) {
+  return stage_guard([&] { return stage_random_impl(e, n_docs, docs, agent, n_ops, seed); });
 }
 
 int crdt_reset_async(crdt_engine* e) {

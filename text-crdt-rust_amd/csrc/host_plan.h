@@ -32,16 +32,20 @@ struct WireView {
     };
     u32 magic, nn;
     if (!rd(magic) || magic != 0x31585452u || !rd(nn)) return false;
+    // the counts are a peer's words: each is checked against the bytes that remain (a name takes at
+    // least its length word, a txn its four header words) before anything is sized by it
+    if (4ull * nn > len - off) return false;
     names.resize(nn);
     for (u32 i = 0; i < nn; i++) {
       u32 bl;
-      if (!rd(bl) || off + bl > len) return false;
+      if (!rd(bl) || bl > len - off) return false;
       names[i].assign((const char*)p + off, bl);
-      off += (bl + 3) & ~3u;
+      off += ((size_t)bl + 3) & ~(size_t)3;
     }
     u32 nt;
     if (!rd(nt)) return false;
     if (off % 4) return false;
+    if (16ull * nt > len - off) return false;
     txns.resize(nt);
     for (u32 t = 0; t < nt; t++) {
       WireTxnView& x = txns[t];
@@ -259,7 +263,10 @@ inline void encode_remote(std::vector<Rec>& out, StreamNeeds& nd, AgentTable& at
         continue;
       }
     }
-    if (t.n_ops > RTXN_NOPS_MASK) zero = true;  // (no stream holds such a txn: rejected as malformed)
+    // a count that does not fit its header field (26 bits of ops, 16 bits of parents) marks the
+    // txn malformed like a zero-length op: the replay stops the document at the header
+    // (ST_BAD_INPUT) instead of reading the records behind a truncated count as txn headers
+    if (t.n_ops > RTXN_NOPS_MASK || t.n_parents > 0xFFFFu) zero = true;
     out.push_back(Rec{(REC_RTXN << 28) | ((zero ? 1u : 0u) << 27) | (has_del << RTXN_DEL_BIT) | (t.n_ops & RTXN_NOPS_MASK),
                       (author & 0xFFFFu) | ((t.n_parents & 0xFFFFu) << 16), t.seq, tl32});
     for (u32 k = 0; k < t.n_ops; k++) {
